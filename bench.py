@@ -21,7 +21,13 @@ With --arith exact (fp32 MFMA, T = 8) every schedule is
 bit-identical to a per-scan in-place update (tests/test_gpu_parity.py::
 test_deferred_flush_equals_drained). The timed region ends with ekf_sync, which flushes the
 partial group: every step's downdate is in P. HIP events in the timed region bracket the flush
-kernel only; the association-kernel time is measured on extra steps after it.
+kernel only.
+
+A plain run stops there: set-up, pre-roll, warm-up, the K timed steps, the result line
+(`kernel_ms.scan`, `cpu_baseline` null; no `parity`). --dump-outputs DIR writes what the last
+timed step left (dump_outputs below) before anything else runs. --full adds the legs that take
+runs of their own: the association-kernel time, measured on W extra steps after the timed region,
+and (one rank, unless --no-cpu) the parity leg and the CPU baseline described below.
 
 roofline: the dominant kernel is the covariance flush (rank-2m MFMA downdate of every step of the
 group, one read + write of the packed block). The timed steps may end in a partial group, whose
@@ -33,7 +39,7 @@ whichever roof is the longer ideal time; durations come from HIP events recorded
 the kernel runs on. `traffic` (HBM bytes per launch of that form from FETCH_SIZE/WRITE_SIZE,
 gfx950-corrected) is read from profiles/<round>/traffic.json only if it was measured on this very
 library build (sha256 of libslam_ekf.so) and configuration; otherwise null.
-cpu_baseline (rank 0, N=1 only): B1, the CPU restatement (oracle/, fast mode, fp64) built with
+cpu_baseline (--full; rank 0, N=1 only): B1, the CPU restatement (oracle/, fast mode, fp64) built with
 OpenMP on the host cores (bit-identical to its single-thread build), timed on a bounded sample of
 the same scans of instance 0; `reference_path` carries B0 (faithful GSL-order restatement, 1 core)
 at the same N from profiles/*cpu_baselines.jsonl, measured once on the GPU box's host (≈minutes
@@ -75,8 +81,15 @@ def parse():
     ap.add_argument("--instances", type=int, default=8, help="EKF instances per GPU")
     ap.add_argument("--precision", choices=["f32", "f64", "f16"], default="f32",
                     help="landmark-block storage (f16: fp32 MFMA accumulation, BASELINE config 5)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the "
+                         "association-kernel timing (kernel_ms.scan), the parity leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last of them left (results, y, pose, a "
+                         "fixed sample of P's rows per instance) as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget (--full)")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="with --full: skip the parity and CPU-baseline legs (a plain run has neither)")
     ap.add_argument("--pipeline", type=int, default=0,
                     help="1: overlap the association kernels with the previous group's flush")
     ap.add_argument("--flush-interval", type=int, default=0,
@@ -118,10 +131,10 @@ def parse():
     ap.add_argument("--traffic-json", default="",
                     help="HBM traffic file (default: the newest profiles/*/traffic.json)")
     args = ap.parse_args()
-    if args.force_collective and not args.no_cpu:
+    if args.force_collective and args.full and not args.no_cpu:
         # the parity leg replays the timed steps from the broadcast's receive groups, which the
         # forced collective has already retired (it is a test of the RCCL branch, not a line)
-        ap.error("--force-collective needs --no-cpu")
+        ap.error("--force-collective with --full needs --no-cpu")
     return args
 
 
@@ -184,6 +197,42 @@ def reference_path_baseline(N):
 def rel(a, b):
     nb = np.linalg.norm(b)
     return float(np.linalg.norm(a - b) / (nb if nb > 0 else 1.0))
+
+
+DUMP_P_BYTES = 48 << 20   # --dump-outputs: P's sampled rows, all ranks together (the rest is < 1 MB)
+
+
+def dump_outputs(path, ens, first, rank, world):
+    """--dump-outputs: what a caller holds after the last timed step (and the closing ekf_sync):
+    every instance's result record, y, pose and savedLineCount, P's diagonal and a fixed sample of
+    P's rows (all of them if they fit the budget; always the three pose rows, the others drawn
+    once from a fixed seed, the same for every instance and run). Everything in float64, as
+    ekf_download_state and ekf_read_results return it (the robot block is kept in fp64 whatever the
+    landmark storage: no narrower width holds every entry exactly). One
+    rank writes <name>.npy, rank r of several <name>_rank<r>.npy (instances first..first+E-1)."""
+    os.makedirs(path, exist_ok=True)
+    E, n = ens.instances, ens.n
+    R = int(min(n, max(3, DUMP_P_BYTES // (world * E * n * 8))))
+    rows = np.arange(n) if R == n else np.concatenate(
+        [np.arange(3), np.sort(3 + np.random.default_rng(4096).choice(n - 3, size=R - 3, replace=False))])
+    res = ens.read_results()
+    P_rows, P_diag = np.empty((E, R, n)), np.empty((E, n))
+    y, pose, saved = np.empty((E, n)), np.empty((E, 3)), np.empty(E)
+    for e in range(E):
+        P, y[e], saved[e], pose[e] = ens.download_state(e)
+        P_rows[e], P_diag[e] = P[rows], np.diagonal(P)
+        del P
+    L = max(len(r["match"]) for r in res)
+    match = np.full((E, L), -2.0)   # (-1: no match; -2: past the instance's line count)
+    for e, r in enumerate(res):
+        match[e, :len(r["match"])] = r["match"]
+    out = {"P_rows": P_rows, "P_row_index": rows.astype(np.float64), "P_diag": P_diag, "y": y, "pose": pose,
+           "saved": saved, "result_pose": np.array([r["pose"] for r in res], dtype=np.float64), "match": match,
+           "result_counts": np.array([[r["matches"], r["new_landmarks"], r["saved"], r["reset"], r["status"]]
+                                      for r in res], dtype=np.float64),
+           "first_instance": np.array([first], dtype=np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
 
 
 PARITY_BAR = {"f32": 1e-6, "f16": 1e-3, "f64": 1e-10}   # ‖ΔP‖_F/‖P‖_F (SURVEY §8d; fp16 re-stated, DESIGN §4.5)
@@ -346,7 +395,7 @@ def main():
 
     # ---- pre-generated scan payloads, resident in HBM (rank 0 is the sensor) ----
     PR = max(0, args.preroll)
-    steps_total = PR + W + K + W
+    steps_total = PR + W + K + (W if args.full else 0)   # (--full: W more for the association timing)
     per_step = D.payload_len(E_total, L_LINES)
     payload = torch.empty((steps_total, per_step), dtype=torch.float64, device=dev)
     if rank == 0:
@@ -406,14 +455,18 @@ def main():
     prof = ens.profile_read()
     flushes = ens.profile_flushes()
     ens.profile(0)
-    # association-kernel time (informational): a few more steps with every kernel timed, outside
-    # the timed region
-    ens.profile(2)
-    for s in range(W):
-        step(PR + W + K + s)
-    ens.sync()
-    scan_ms = ens.profile_read()["scan_ms"]
-    ens.profile(0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ens, first, rank, world)
+    # association-kernel time (--full, informational): a few more steps with every kernel timed,
+    # outside the timed region
+    scan_ms = None
+    if args.full:
+        ens.profile(2)
+        for s in range(W):
+            step(PR + W + K + s)
+        ens.sync()
+        scan_ms = ens.profile_read()["scan_ms"]
+        ens.profile(0)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if host_coll else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -543,7 +596,7 @@ def main():
         out["last_step_results"] = [{"matches": r["matches"], "saved": r["saved"],
                                      "reset": r["reset"], "status": r["status"]} for r in res]
 
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         from oracle import oracle as O
         cores = O.threads(True)
         host = payload.cpu().numpy()

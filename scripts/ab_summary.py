@@ -17,7 +17,9 @@ for f in sorted(glob.glob(os.path.join(d, "bench_*.json"))):
     pr = next((json.loads(l) for l in open(pf) if l.startswith("{")), None) if os.path.exists(pf) else None
     row = [name]
     if b:
-        row += [f"{b['value']/1e3:.1f}k", f"scan {b['kernel_ms']['scan']*1e3:.1f}", f"flush {b['kernel_ms']['flush']*1e3:.0f}"]
+        scan = b["kernel_ms"]["scan"]   # (null unless the line was run with bench.py --full)
+        row += [f"{b['value']/1e3:.1f}k", f"scan {scan*1e3:.1f}" if scan is not None else "scan -",
+                f"flush {b['kernel_ms']['flush']*1e3:.0f}"]
     if pr:
         row += [f"{k.split('(')[0]} {pr['us'].get(k, float('nan')):.2f}" for k in keys]
     rows.append("  ".join(row))

@@ -10,6 +10,6 @@ rc=$?
 echo "pytest rc $rc" > $OUT/status
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1 || { echo "smoke failed" >> $OUT/status; exit 3; }
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed" >> $OUT/status; exit 4; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed" >> $OUT/status; exit 4; }
 echo "done pytest_rc=$rc" >> $OUT/status
 exit $rc

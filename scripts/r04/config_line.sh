@@ -16,7 +16,7 @@ timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $GRAFT_REPO_ROO
 timeout -s KILL 240 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE GRBM_COUNT --kernel-trace -d $GRAFT_REPO_ROOT/$OUT/sq -o run --output-format csv -- python3 bench.py --no-cpu "$@" > $OUT/sq.log 2>&1 && \
 timeout -s KILL 240 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM SQ_INSTS_BRANCH SQ_INSTS_VALU_FMA_F64 --kernel-trace -d $GRAFT_REPO_ROOT/$OUT/insts -o run --output-format csv -- python3 bench.py --no-cpu "$@" > $OUT/insts.log 2>&1 && \
 timeout -k 10 120 python scripts/pmc_summary.py $TAG $OUT/profile > $OUT/summary.log 2>&1 && \
-timeout -k 10 400 python bench.py --traffic-json $OUT/profile/traffic.json "$@" > $OUT/bench_full.json 2> $OUT/bench_full.err
+timeout -k 10 400 python bench.py --full --traffic-json $OUT/profile/traffic.json "$@" > $OUT/bench_full.json 2> $OUT/bench_full.err
 rc=$?
 echo "exit $rc" >> $OUT/status
 exit $rc
