@@ -188,7 +188,13 @@ enum {
      * cross-workgroup exchange per line), 2 test hook: every guess wrong (the speculative path,
      * a failed verdict and the sequential restart on every scan), 3 test hook: the guesses of
      * lines L/2 .. L-1 wrong (a failed verdict keeps the lines before the first wrong one).
-     * Identical results. */
+     * Results: bit-identical in all four modes under EKF_ARITH_EXACT and on fp64 storage, and on
+     * the split arithmetics with the per-element replay (EKF_OPT_MFMA_REPLAY off: it is the
+     * sequential chain). On the split arithmetics with the MFMA replay (1 or 2) the association,
+     * matches, new landmarks and status of every scan are identical and the state is within the
+     * arithmetic's parity bar of the fp64 reference in every mode, but not the same bits: mode 0
+     * reads the pending steps by the exact per-step chain, the speculative pass by MFMA, and a
+     * restart takes the guessed columns from the MFMA replay and the others from the chain. */
     EKF_OPT_SPECULATE = 1,
     /* spin bound of the association's cross-workgroup waits: 2^v polls, 8 <= v <= 24 (24) */
     EKF_OPT_SPIN_LOG2 = 2,

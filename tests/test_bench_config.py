@@ -44,8 +44,10 @@ def rel(a, b):
     return float(np.linalg.norm(a - b) / (nb if nb > 0 else 1.0))
 
 
-def record(key, value):
+def record(key, value, name=None):
     path = os.path.join(ROOT, "gpurun_out", "bench_config_parity.json")
+    if name:   # another module's record, next to this one
+        path = os.path.join(os.path.dirname(path), name)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     data = json.load(open(path)) if os.path.exists(path) else {}
     data[key] = value

@@ -298,6 +298,56 @@ def test_synchronous_result_mirror(ekf_mod, prec, T):
     ens.close()
 
 
+@pytest.mark.parametrize("prec,T", [(0, 1), (1, 4), (2, 8)])
+def test_result_mirror_invalidated_by_reset_and_init(ekf_mod, prec, T):
+    """ekf_get_pose_cov serves the pinned mirror of the last synchronous scan until the robot block
+    changes without a scan. ekf_reset_instance and ekf_init_lowrank change it (each clears the
+    mirror by hand, as ekf_upload_state does, checked above): after a scan, the very next
+    ekf_get_pose_cov after either call must be the new block — equal to the downloaded state's
+    top-left 3 × 3 and different from the block the mirror holds, so a stale mirror fails. The
+    instances not touched keep theirs.
+
+    ekf_rescale clears the mirror too but cannot change the robot block: it re-packs the landmark
+    block (rows and columns >= 3) under another fp16 exponent, the robot strip is stored in fp64
+    and passes through unpack / pack unchanged (and on fp64 / fp32 storage the call does nothing).
+    A stale mirror would serve the same values, so there is nothing to assert for it here."""
+    N, E = 100, 3
+    w = G.make_world(N)
+    st = G.initial_state(w)
+    ens = ekf_mod.Ensemble(N, E, prec, max_lines=8, flush_interval=T)
+    for e in range(E):
+        ens.init_lowrank(e, st.diag, st.U, st.y, st.saved, st.pose)
+
+    def scan(step):
+        enc, ln, nl = G.make_scan(w, step, instances=E)
+        ens.localize(enc, ln, nl)
+        return [ens.pose_cov(e) for e in range(E)]   # (the mirror: the call right after the scan)
+
+    def check(e, before, what):
+        after = ens.pose_cov(e)                       # the very next call
+        others = {o: ens.pose_cov(o) for o in range(E) if o != e}
+        P = ens.download_state(e)[0]
+        np.testing.assert_array_equal(after, P[:3, :3], err_msg=what)
+        assert np.all(after.diagonal() != before[e].diagonal()), (what, "the block did not change", after, before[e])
+        for o, blk in others.items():
+            np.testing.assert_array_equal(blk, before[o], err_msg=f"{what}: instance {o}")
+            np.testing.assert_array_equal(blk, ens.download_state(o)[0][:3, :3], err_msg=f"{what}: instance {o}")
+
+    before = scan(1)
+    ens.reset(1, 0.5, -0.25, 0.1)                     # Robot::Robot: its own P_t0
+    check(1, before, "reset")
+    before = scan(2)
+    ens.init_lowrank(2, 2.0 * st.diag, 1.5 * st.U, st.y, st.saved, st.pose)
+    check(2, before, "init_lowrank")
+    before = scan(3)
+    ens.reset(-1, 0.0, 0.0, 0.0)                      # every instance
+    for e in range(E):
+        after = ens.pose_cov(e)
+        np.testing.assert_array_equal(after, ens.download_state(e)[0][:3, :3])
+        assert np.all(after.diagonal() != before[e].diagonal()), (e, after, before[e])
+    ens.close()
+
+
 @pytest.mark.parametrize("prec", [0, 1, 2])
 def test_ensemble_instances_are_independent(ekf_mod, prec):
     N, E = 64, 3
