@@ -51,6 +51,8 @@ struct ekf_ctx {
     long long t0 = 0, t1 = 0; // tiles stored per instance [t0, t1): all, unless partitioned (ekf_shard_create)
     size_t xinst;             // stored landmark-block elements per instance ((t1 − t0)·TILE_ELEMS)
     size_t op_inst;           // operand elements per instance
+    std::vector<void*> dev_mem;      // every device buffer create_ctx made (dev_alloc), freed by free_all
+    std::vector<void*> pinned_mem;   // ... and every pinned host buffer (pinned_alloc)
     void* X[2];
     double* Rs;               // [2][E][3][n] robot strip, two copies (the association kernel reads
     double* y;                // [2][E][n]    copy cur[e] and writes the other; the lead commits it)
@@ -208,30 +210,42 @@ int ekf_abi_version(void) { return SLAM_EKF_ABI_VERSION; }
 
 }  // extern "C"
 
+// The context's memory: every buffer create_ctx makes goes through these two and is freed from the
+// lists (free_all); only the buffers made or remade later are freed by name
+static bool dev_alloc(ekf_ctx* c, void** p, size_t bytes)
+{
+    if (hipMalloc(p, bytes) != hipSuccess) return false;
+    c->dev_mem.push_back(*p);
+    return hipMemset(*p, 0, bytes) == hipSuccess;
+}
+
+static bool pinned_alloc(ekf_ctx* c, void** p, size_t bytes)
+{
+    if (hipHostMalloc(p, bytes) != hipSuccess) return false;
+    c->pinned_mem.push_back(*p);
+    return true;
+}
+
+// A host-built table (ekf_tables.h) into device memory of its own; *count: its entries
+static_assert(sizeof(ekf::TileRC) == sizeof(int2) && alignof(ekf::TileRC) <= alignof(int2) &&
+                  offsetof(ekf::TileRC, x) == offsetof(int2, x) && offsetof(ekf::TileRC, y) == offsetof(int2, y),
+              "ekf::TileRC is the kernels' int2");
+template <typename D, typename V>
+static bool upload_table(ekf_ctx* c, D** dst, const std::vector<V>& table, int* count = nullptr)
+{
+    static_assert(sizeof(D) == sizeof(V), "the table's entries as the kernels read them");
+    const size_t bytes = sizeof(V) * table.size();
+    if (count) *count = (int)table.size();
+    return dev_alloc(c, (void**)dst, bytes) && hipMemcpy(*dst, table.data(), bytes, hipMemcpyHostToDevice) == hipSuccess;
+}
+
 static void free_all(ekf_ctx* c)
 {
-    std::vector<void*> ptrs = {c->X[0], c->X[1], c->Rs, c->y, c->cur, c->pose, c->xpre, c->saved, c->D,
-                               c->tile_rc, c->stile_rc, c->stile2_rc, c->wt, c->wt64, c->wt24, c->wtq, c->d_in, c->dbg, c->pexp, c->sink, c->mbox,
-                               c->sync, c->Ust, c->Vst, c->dense, c->psig, c->pvmax,
-                               c->sh_rob, c->sh_rec, c->sh_hist, c->sh_pkg, c->sh_flags, c->sh_ctl,
-                               c->sh_null.res, c->sh_xbuf, c->sh_xcols};
-    ptrs.push_back(c->ops_u);
-    ptrs.push_back(c->ops_v);
-    ptrs.push_back(c->ops_b);
-    for (auto& sl : c->ring) {
-        ptrs.push_back(sl.patch);
-        ptrs.push_back(sl.patch_diag);
-        ptrs.push_back(sl.res);
-    }
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    for (void* p : c->dev_mem) (void)hipFree(p);
+    for (void* p : {(void*)c->dbg, (void*)c->dense, (void*)c->sh_xbuf, (void*)c->sh_xcols}) (void)hipFree(p);   // (or null)
+    for (void* p : c->pinned_mem) (void)hipHostFree(p);
     if (c->h_agree) (void)hipHostFree(c->h_agree);
-    if (c->h_res) (void)hipHostFree(c->h_res);
-    if (c->h_pose) (void)hipHostFree(c->h_pose);
-    if (c->h_r33) (void)hipHostFree(c->h_r33);
-    if (c->h_in) (void)hipHostFree(c->h_in);
     if (c->ev_in) (void)hipEventDestroy(c->ev_in);
-    if (c->h_ep) (void)hipHostFree(c->h_ep);
     for (auto& v : c->ev)
         for (auto& pr : v) { (void)hipEventDestroy(pr.a); (void)hipEventDestroy(pr.b); }
     for (auto& pr : c->pool) { (void)hipEventDestroy(pr.a); (void)hipEventDestroy(pr.b); }
@@ -258,6 +272,16 @@ static int drain(ekf_ctx* c)
     c->pend0 = c->nsteps;
     c->ev_base = nullptr;
     return EKF_OK;
+}
+
+// Every entry point that writes an instance's state without a scan (reset, upload, low-rank
+// initialisation, rescale, and any added later) starts here: the synchronous calls' result mirror
+// holds the robot block of the last scan, which the write makes stale (ekf_get_pose_cov must not
+// serve it), and the write needs the materialised landmark block.
+static int begin_state_write(ekf_ctx* c)
+{
+    c->mirror_epoch = 0;
+    return drain(c);
 }
 
 static inline int cur_buf(const ekf_ctx* c) { return c->last_out; }
@@ -347,25 +371,6 @@ static int set_robot_ctor(ekf_ctx* c, int e, double x, double y, double th)
     return set_exponent(c, e, c->cfg.precision == EKF_PREC_F16 ? ekf::F16_EXP_DEFAULT : 0);
 }
 
-// One packed-tile-row partition of the landmark block over `world` ranks: boundaries on even tile
-// rows (whole wave-tile rows of the flush) balancing the tiles per rank; rank's rows [r0, r1)
-static void tile_partition(int nb, int world, int rank, int& r0, int& r1)
-{
-    const long long total = (long long)nb * (nb + 1) / 2;
-    auto boundary = [&](int k) {
-        if (k <= 0) return 0;
-        if (k >= world) return nb;
-        // the even tile row whose prefix of tiles is closest to k/world of them
-        const long long want = total * k / world;
-        int bi = 0;
-        while (bi + 2 < nb && ekf::tile_index(bi + 2, bi + 2, nb) <= want) bi += 2;
-        if (bi + 2 < nb && ekf::tile_index(bi + 2, bi + 2, nb) - want < want - ekf::tile_index(bi, bi, nb)) bi += 2;
-        return bi;
-    };
-    r0 = boundary(rank);
-    r1 = boundary(rank + 1);
-}
-
 static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx** out);
 
 extern "C" int ekf_create(const ekf_config* cfg, ekf_ctx** out)
@@ -427,7 +432,7 @@ static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx*
     c->t0 = 0;
     c->t1 = d.ntiles;
     if (sh_world > 0) {
-        tile_partition(d.nb, sh_world, sh_rank, c->sh_r0, c->sh_r1);
+        ekf::tile_partition(d.nb, sh_world, sh_rank, c->sh_r0, c->sh_r1);
         if (c->sh_r0 >= c->sh_r1) {   // more ranks than wave-tile rows
             delete c;
             return EKF_ERANGE;
@@ -448,11 +453,7 @@ static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx*
     // nothing would overlap: such contexts run the sequential schedule (slam_ekf.h)
     if (c->G > 1) c->cfg.pipeline = 0;
     int rc = EKF_ENOMEM;
-#define ALLOC(ptr, bytes)                                                       \
-    do {                                                                        \
-        if (hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) goto fail;        \
-        if (hipMemset((void*)(ptr), 0, (bytes)) != hipSuccess) goto fail;       \
-    } while (0)
+#define ALLOC(ptr, bytes) do { if (!dev_alloc(c, (void**)&(ptr), (bytes))) goto fail; } while (0)
     ALLOC(c->X[0], c->xinst * c->elem * E);
     if (c->cfg.pipeline) ALLOC(c->X[1], c->xinst * c->elem * E);
     else c->X[1] = nullptr;
@@ -494,11 +495,19 @@ static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx*
         ALLOC(sl.patch_diag, sizeof(double) * d.max_lines * 4 * E);
         ALLOC(sl.res, sizeof(int) * ekf::RES_STRIDE * E);
     }
-    ALLOC(c->tile_rc, sizeof(int2) * d.ntiles);
     {
-        const int nsb = (d.nb + ekf::DD_SB - 1) / ekf::DD_SB;
-        ALLOC(c->stile_rc, sizeof(int2) * (size_t)nsb * (nsb + 1) / 2);
-        ALLOC(c->stile2_rc, sizeof(int2) * (size_t)nsb * ((d.nb + 1) / 2));
+        // the flush kernels' tile tables (ekf_tables.h). A partitioned instance flushes its tile rows
+        // only: its wave tables keep those rows, and it has no quad table
+        const bool part = c->sh_world > 0;
+        const auto wt = ekf::wt_table(d.nb), wt64 = ekf::wt64_table(d.nb);
+        if (!upload_table(c, &c->tile_rc, ekf::tile_rc_table(d.nb)) ||
+            !upload_table(c, &c->stile_rc, ekf::stile_rc_table(d.nb)) ||
+            !upload_table(c, &c->stile2_rc, ekf::stile2_rc_table(d.nb), &c->nstiles2) ||
+            !upload_table(c, &c->wt, part ? ekf::keep_tile_rows(wt, ekf::WT_R, c->sh_r0, c->sh_r1) : wt, &c->nwt) ||
+            !upload_table(c, &c->wt64, part ? ekf::keep_tile_rows(wt64, 1, c->sh_r0, c->sh_r1) : wt64, &c->nwt64) ||
+            !upload_table(c, &c->wt24, ekf::wt24_table(d.nb), &c->nwt24) ||
+            (!part && !upload_table(c, &c->wtq, ekf::wtq_table(d.nb), &c->nwtq)))
+            goto fail;
     }
     c->in_lines = ((sizeof(double) * 3 * E + 15) / 16) * 16;
     c->in_nlines = c->in_lines + ((sizeof(ekf_line) * d.max_lines * E + 15) / 16) * 16;
@@ -543,11 +552,12 @@ static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx*
     c->sync_stride = ((ekf::SYNC_WG0 + c->Gmax + 15) / 16) * 16;
     ALLOC(c->sync, sizeof(int) * c->sync_stride * E);
 #undef ALLOC
-    if (hipHostMalloc((void**)&c->h_res, sizeof(int) * ekf::RES_STRIDE * E) != hipSuccess) goto fail;
-    if (hipHostMalloc((void**)&c->h_pose, sizeof(double) * 3 * E) != hipSuccess) goto fail;
-    if (hipHostMalloc((void**)&c->h_r33, sizeof(double) * 9 * E) != hipSuccess) goto fail;
-    if (hipHostMalloc((void**)&c->h_ep, sizeof(unsigned) * E) != hipSuccess) goto fail;
-    if (hipHostMalloc((void**)&c->h_in, c->in_bytes) != hipSuccess) goto fail;
+    if (!pinned_alloc(c, (void**)&c->h_res, sizeof(int) * ekf::RES_STRIDE * E) ||
+        !pinned_alloc(c, (void**)&c->h_pose, sizeof(double) * 3 * E) ||
+        !pinned_alloc(c, (void**)&c->h_r33, sizeof(double) * 9 * E) ||
+        !pinned_alloc(c, (void**)&c->h_ep, sizeof(unsigned) * E) ||
+        !pinned_alloc(c, (void**)&c->h_in, c->in_bytes))
+        goto fail;
     if (hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming) != hipSuccess) goto fail;
     memset(c->h_ep, 0, sizeof(unsigned) * E);
     if (hipHostGetDevicePointer((void**)&c->hd_res, c->h_res, 0) != hipSuccess ||
@@ -563,170 +573,6 @@ static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx*
     for (int k = 0; k < 2; k++)
         if (hipEventCreateWithFlags(&c->ev_flush[k], hipEventDisableTiming) != hipSuccess) goto fail;
     {
-        std::vector<int2> rcv((size_t)d.ntiles);
-        for (int bi = 0; bi < d.nb; bi++)
-            for (int bj = bi; bj < d.nb; bj++) {
-                int2 v;
-                v.x = bi;
-                v.y = bj;
-                rcv[(size_t)ekf::tile_index(bi, bj, d.nb)] = v;
-            }
-        if (hipMemcpy(c->tile_rc, rcv.data(), sizeof(int2) * d.ntiles, hipMemcpyHostToDevice) !=
-            hipSuccess)
-            goto fail;
-        const int nsb = (d.nb + ekf::DD_SB - 1) / ekf::DD_SB;
-        std::vector<int2> srcv;
-        for (int bi = 0; bi < nsb; bi++)
-            for (int bj = bi; bj < nsb; bj++) {
-                int2 v;
-                v.x = bi;
-                v.y = bj;
-                srcv.push_back(v);
-            }
-        if (hipMemcpy(c->stile_rc, srcv.data(), sizeof(int2) * srcv.size(), hipMemcpyHostToDevice) !=
-            hipSuccess)
-            goto fail;
-        // 4 × 2 super-tiles holding at least one stored tile (bi <= bj): sbj·2 + 1 >= sbi·4
-        std::vector<int2> s2;
-        for (int si = 0; si < nsb; si++)
-            for (int sj = 0; sj < (d.nb + 1) / 2; sj++)
-                if (sj * 2 + 1 >= si * 4) {
-                    int2 v;
-                    v.x = si;
-                    v.y = sj;
-                    s2.push_back(v);
-                }
-        c->nstiles2 = (int)s2.size();
-        if (hipMemcpy(c->stile2_rc, s2.data(), sizeof(int2) * s2.size(), hipMemcpyHostToDevice) !=
-            hipSuccess)
-            goto fail;
-        // WT_R × WT_C wave-tiles holding a stored tile (wc·WT_C + WT_C − 1 >= wr·WT_R), in panels
-        // of 16 wave-tile columns walked row by row (the wave-tiles an XCD has in flight share
-        // operand rows); each entry carries its tile indices and operand row blocks
-        const int nwr = (d.nb + ekf::WT_R - 1) / ekf::WT_R, nwc = (d.nb + ekf::WT_C - 1) / ekf::WT_C;
-        std::vector<ekf::WtEntry> wt;
-        for (int pc = 0; pc < nwc; pc += 16)
-            for (int wr = 0; wr < nwr; wr++)
-                for (int wc = pc; wc < pc + 16 && wc < nwc; wc++) {
-                    if (wc * ekf::WT_C + ekf::WT_C - 1 < wr * ekf::WT_R) continue;
-                    ekf::WtEntry v;
-                    memset(&v, 0, sizeof(v));
-                    // a stored tile of this wave-tile (its first row, last column in the block)
-                    const int fbi = wr * ekf::WT_R, fbj = std::min(wc * ekf::WT_C + ekf::WT_C - 1, d.nb - 1);
-                    for (int r = 0; r < ekf::WT_R; r++)
-                        for (int cc = 0; cc < ekf::WT_C; cc++) {
-                            const int i = r * ekf::WT_C + cc;
-                            const int bi = wr * ekf::WT_R + r, bj = wc * ekf::WT_C + cc;
-                            const bool ok = bi < d.nb && bj < d.nb && bi <= bj;
-                            v.tile[i] = (int)(ok ? ekf::tile_index(bi, bj, d.nb) : ekf::tile_index(fbi, fbj, d.nb));
-                            v.valid |= (ok ? 1 : 0) << i;
-                        }
-                    for (int r = 0; r < ekf::WT_R; r++)
-                        v.rows[0] |= std::min(wr * ekf::WT_R + r, d.nb - 1) << (16 * r);
-                    for (int cc = 0; cc < ekf::WT_C; cc++)
-                        v.rows[1] |= std::min(wc * ekf::WT_C + cc, d.nb - 1) << (16 * cc);
-                    v.rc = wr | (wc << 16);
-                    wt.push_back(v);
-                }
-        if (c->sh_world > 0) {   // a partitioned instance flushes its tile rows only
-            std::vector<ekf::WtEntry> keep;
-            for (const auto& v : wt) {
-                const int r = (v.rc & 0xffff) * ekf::WT_R;
-                if (r >= c->sh_r0 && r < c->sh_r1) keep.push_back(v);
-            }
-            wt.swap(keep);
-        }
-        c->nwt = (int)wt.size();
-        if (hipMalloc((void**)&c->wt, sizeof(ekf::WtEntry) * wt.size()) != hipSuccess) goto fail;
-        if (hipMemcpy(c->wt, wt.data(), sizeof(ekf::WtEntry) * wt.size(), hipMemcpyHostToDevice) !=
-            hipSuccess)
-            goto fail;
-        // the f64 wave flush: wave-tiles of 1 × WT64_C tiles, same panel walk
-        std::vector<ekf::WtEntry> w64;
-        const int nwc64 = (d.nb + ekf::WT64_C - 1) / ekf::WT64_C;
-        for (int pc = 0; pc < nwc64; pc += 16)
-            for (int wr = 0; wr < d.nb; wr++)
-                for (int wc = pc; wc < pc + 16 && wc < nwc64; wc++) {
-                    if (wc * ekf::WT64_C + ekf::WT64_C - 1 < wr) continue;
-                    ekf::WtEntry v;
-                    memset(&v, 0, sizeof(v));
-                    const int fbj = std::min(wc * ekf::WT64_C + ekf::WT64_C - 1, d.nb - 1);   // stored
-                    for (int cc = 0; cc < ekf::WT64_C; cc++) {
-                        const int bj = wc * ekf::WT64_C + cc;
-                        const bool ok = bj < d.nb && wr <= bj;
-                        v.tile[cc] = (int)(ok ? ekf::tile_index(wr, bj, d.nb) : ekf::tile_index(wr, fbj, d.nb));
-                        v.valid |= (ok ? 1 : 0) << cc;
-                        v.rows[1] |= std::min(bj, d.nb - 1) << (16 * cc);
-                    }
-                    v.rows[0] = wr;
-                    v.rc = wr | (wc << 16);
-                    w64.push_back(v);
-                }
-        if (c->sh_world > 0) {
-            std::vector<ekf::WtEntry> keep;
-            for (const auto& v : w64)
-                if (v.rows[0] >= c->sh_r0 && v.rows[0] < c->sh_r1) keep.push_back(v);
-            w64.swap(keep);
-        }
-        c->nwt64 = (int)w64.size();
-        if (hipMalloc((void**)&c->wt64, sizeof(ekf::WtEntry) * w64.size()) != hipSuccess) goto fail;
-        if (hipMemcpy(c->wt64, w64.data(), sizeof(ekf::WtEntry) * w64.size(), hipMemcpyHostToDevice) !=
-            hipSuccess)
-            goto fail;
-        // the split-bf16 flush's 2 × 4 wave-tiles holding a stored tile (4wc + 3 >= 2wr), in panels of
-        // 8 wave-tile columns walked row by row (flush_bf24_kernel)
-        std::vector<int> w24;
-        const int nwr2 = (d.nb + 1) / 2, nwc4 = (d.nb + 3) / 4;
-        for (int pc = 0; pc < nwc4; pc += 8)
-            for (int wr = 0; wr < nwr2; wr++)
-                for (int wc = pc; wc < pc + 8 && wc < nwc4; wc++)
-                    if (4 * wc + 3 >= 2 * wr) w24.push_back(wr | (wc << 16));
-        c->nwt24 = (int)w24.size();
-        if (hipMalloc((void**)&c->wt24, sizeof(int) * w24.size()) != hipSuccess) goto fail;
-        if (hipMemcpy(c->wt24, w24.data(), sizeof(int) * w24.size(), hipMemcpyHostToDevice) != hipSuccess)
-            goto fail;
-        // the split-fp16 quad form's groups of 2 × 2 wave-tiles holding a stored tile (group column
-        // >= group row), in panels of 8 group columns walked row by row; entry 2a + b of a group is
-        // its wave-tile (2R + a, 2C + b). Wave-tiles wholly below the diagonal or past the block stay
-        // in their group (the group's operand rows are loaded alike): no valid tile, indices of a
-        // stored tile of the group, rows clamped to the block. A partitioned context has none.
-        if (c->sh_world <= 0) {
-            std::vector<ekf::WtEntry> wq;
-            const int ngr = (nwr + 1) / 2, ngc = (nwc + 1) / 2;
-            for (int pc = 0; pc < ngc; pc += 8)
-                for (int R = 0; R < ngr; R++)
-                    for (int Cg = pc; Cg < pc + 8 && Cg < ngc; Cg++) {
-                        if (Cg < R) continue;
-                        // a stored tile of the group: its first tile row, last tile column in the block
-                        const long long any = ekf::tile_index(4 * R, std::min(4 * Cg + 3, d.nb - 1), d.nb);
-                        for (int a = 0; a < 2; a++)
-                            for (int b = 0; b < 2; b++) {
-                                const int wr = 2 * R + a, wc = 2 * Cg + b;
-                                ekf::WtEntry v;
-                                memset(&v, 0, sizeof(v));
-                                for (int r = 0; r < ekf::WT_R; r++)
-                                    for (int cc = 0; cc < ekf::WT_C; cc++) {
-                                        const int i = r * ekf::WT_C + cc;
-                                        const int bi = wr * ekf::WT_R + r, bj = wc * ekf::WT_C + cc;
-                                        const bool ok = bi < d.nb && bj < d.nb && bi <= bj;
-                                        v.tile[i] = (int)(ok ? ekf::tile_index(bi, bj, d.nb) : any);
-                                        v.valid |= (ok ? 1 : 0) << i;
-                                    }
-                                for (int r = 0; r < ekf::WT_R; r++)
-                                    v.rows[0] |= std::min(wr * ekf::WT_R + r, d.nb - 1) << (16 * r);
-                                for (int cc = 0; cc < ekf::WT_C; cc++)
-                                    v.rows[1] |= std::min(wc * ekf::WT_C + cc, d.nb - 1) << (16 * cc);
-                                v.rc = wr | (wc << 16);
-                                wq.push_back(v);
-                            }
-                    }
-            c->nwtq = (int)wq.size();
-            if (hipMalloc((void**)&c->wtq, sizeof(ekf::WtEntry) * wq.size()) != hipSuccess) goto fail;
-            if (hipMemcpy(c->wtq, wq.data(), sizeof(ekf::WtEntry) * wq.size(), hipMemcpyHostToDevice) != hipSuccess)
-                goto fail;
-        }
-    }
-    {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) goto fail;
         c->dd_per_cu = 8;   // downdate workgroups per CU (4 waves each; EKF_OPT_FLUSH_BLOCKS_PER_CU)
@@ -734,7 +580,7 @@ static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx*
         c->ncu = prop.multiProcessorCount;
         // automatic flush form (EKF_OPT_FLUSH_FORM); a partitioned instance: the wave form for every
         // group (its wave tables hold the rank's tile rows only; the other forms walk every tile)
-        c->dd_variant = c->sh_world > 0 ? 8 : 0;
+        c->dd_variant = c->sh_world > 0 ? ekf::FORM_WAVE : ekf::FORM_AUTO;
         // all G workgroups of an instance must be co-resident (they exchange per line). A plain
         // launch gets the same residency as a cooperative one for the same grid
         // (cdna_hip_programming.md §1; the cooperative form only adds a launch-time check of the
@@ -809,10 +655,10 @@ extern "C" int ekf_set_option(ekf_ctx* c, int opt, int v)
     case EKF_OPT_SPECULATE: if (v < 0 || v > 3) return EKF_ERANGE; break;
     case EKF_OPT_SPIN_LOG2: if (v < 8 || v > 24) return EKF_ERANGE; break;
     case EKF_OPT_FLUSH_FORM:
-        if (v != 0 && v != 2 && v != 8 && v != 24 && v != 44) return EKF_ERANGE;
+        if (!ekf::flush_form_valid(v)) return EKF_ERANGE;
         // a partitioned context stores only its tile rows; only the wave forms walk the rank's
         // wave tables (the super-tile and tile forms walk every tile of the block)
-        if (c->sh_world > 0 && v != 8) return EKF_EINVAL;
+        if (c->sh_world > 0 && v != ekf::FORM_WAVE) return EKF_EINVAL;
         break;
     case EKF_OPT_FLUSH_BLOCKS_PER_CU: if (v < 1 || v > 16) return EKF_ERANGE; break;
     case EKF_OPT_MFMA_REPLAY: if (v < 0 || v > 2) return EKF_ERANGE; break;
@@ -879,10 +725,9 @@ extern "C" int ekf_get_option(const ekf_ctx* c, int opt, int* v)
 
 extern "C" int ekf_reset_instance(ekf_ctx* c, int e, double x, double y, double th)
 {
-    if (c) c->mirror_epoch = 0;   // (the robot block changes without a scan)
     if (!c) return EKF_EINVAL;
     if (e >= c->cfg.instances) return EKF_ERANGE;
-    int rc = drain(c);
+    int rc = begin_state_write(c);
     if (rc) return rc;
     if (e < 0) {
         for (int k = 0; k < c->cfg.instances; k++) {
@@ -1019,11 +864,19 @@ static const ekf::Slot& slot_of(const ekf_ctx* c, long long k)
     return c->ring[(size_t)(k % (long long)c->ring.size())];
 }
 
+// The kernel that flushes a group of nsteps steps of this context (ekf_flush_plan.h)
+static ekf::FlushPlan flush_plan_of(const ekf_ctx* c, int nsteps)
+{
+    return ekf::flush_plan(ekf::FlushKey{c->cfg.precision, c->pmode, c->dd_variant, nsteps, c->d.kmax, c->sh_world > 0,
+                                         c->nwt > 0, c->nwt64 > 0, c->nwt24 > 0, c->nwtq > 0});
+}
+
 // One pass over the landmark block applying steps [unflushed0, nsteps) (stream D).
 static int enqueue_flush(ekf_ctx* c)
 {
     const int nst = (int)(c->nsteps - c->unflushed0);
     if (nst <= 0) return EKF_OK;
+    const ekf::FlushPlan plan = flush_plan_of(c, nst);
     // sequential schedule: the flush follows the scans on S (no cross-stream events); pipelined:
     // on D after the group's last scan
     hipStream_t fs = c->cfg.pipeline ? c->dstream : c->stream;
@@ -1032,7 +885,7 @@ static int enqueue_flush(ekf_ctx* c)
     memset(&dp, 0, sizeof(dp));
     dp.d = c->d;
     dp.E = c->cfg.instances;
-    dp.nsteps = nst;
+    dp.nsteps = plan.nsteps;
     dp.variant = c->dd_variant;
     dp.ncu = c->ncu;
     dp.tile_rc = c->tile_rc;
@@ -1060,12 +913,7 @@ static int enqueue_flush(ekf_ctx* c)
     dp.bbase = c->ops_b;
     dp.bslot_bytes = c->bslot_bytes;
     for (int q = 0; q < nst; q++) dp.steps[q] = slot_of(c, c->unflushed0 + q);
-    if (c->sh_world > 0 && c->cfg.precision == EKF_PREC_F32 && (nst & 1)) {
-        // a partitioned instance flushes with the wave form only (even groups): pad with a step
-        // that applies nothing
-        dp.steps[nst] = c->sh_null;
-        dp.nsteps = nst + 1;
-    }
+    for (int q = nst; q < plan.nsteps; q++) dp.steps[q] = c->sh_null;   // (the plan's padding step)
     const int in = c->last_out;
     const int out = c->cfg.pipeline ? 1 - in : in;
     dp.Pin = xview(c, in);
@@ -1076,7 +924,7 @@ static int enqueue_flush(ekf_ctx* c)
     dp.zskip = (c->active_flush && c->sh_world == 0 && in == out) ? 1 : 0;
     EvPair* pr = prof_begin(c, 1, fs, false);
     if (pr) c->ev_nsteps.push_back(nst);
-    HIP_TRY(ekf::launch_downdate(dp, c->cfg.precision, c->dd_grid, fs, pr ? pr->a : nullptr,
+    HIP_TRY(ekf::launch_downdate(dp, plan, c->dd_grid, fs, pr ? pr->a : nullptr,
                                  pr ? pr->b : nullptr));
     hipEvent_t ev = c->ev_flush[c->nflush & 1];
     if (c->cfg.pipeline) HIP_TRY(hipEventRecord(ev, fs));
@@ -1294,11 +1142,10 @@ static hipError_t dense_scratch(ekf_ctx* c, double** out)
 extern "C" int ekf_upload_state(ekf_ctx* c, int e, const double* P, const double* y, int saved,
                                 const double pose[3])
 {
-    if (c) c->mirror_epoch = 0;   // (the robot block changes without a scan)
     if (!c) return EKF_EINVAL;
     if (e < 0 || e >= c->cfg.instances) return EKF_ERANGE;
     if (saved < 0 || saved > c->d.N) return EKF_ERANGE;
-    int rc = drain(c);
+    int rc = begin_state_write(c);
     if (rc) return rc;
     const Dims& d = c->d;
     int cb = 0;
@@ -1377,10 +1224,9 @@ extern "C" int ekf_download_state(ekf_ctx* c, int e, double* P, double* y, int* 
 extern "C" int ekf_init_lowrank(ekf_ctx* c, int e, const double* diag, const double* U, int rank,
                                 const double* y, int saved, const double pose[3])
 {
-    if (c) c->mirror_epoch = 0;   // (the robot block changes without a scan)
     if (!c || !diag || (rank > 0 && !U) || rank < 0) return EKF_EINVAL;
     if (e < 0 || e >= c->cfg.instances) return EKF_ERANGE;
-    int rc = drain(c);
+    int rc = begin_state_write(c);
     if (rc) return rc;
     const Dims& d = c->d;
     int cb = 0;
@@ -1422,12 +1268,11 @@ extern "C" int ekf_storage_exponent(const ekf_ctx* c, int e)
 
 extern "C" int ekf_rescale(ekf_ctx* c, int e, int ex)
 {
-    if (c) c->mirror_epoch = 0;   // (the robot block changes without a scan)
     if (!c) return EKF_EINVAL;
     if (e < 0 || e >= c->cfg.instances) return EKF_ERANGE;
     if (c->cfg.precision != EKF_PREC_F16) return EKF_OK;
     if (ex != EKF_EXP_AUTO && (ex < -24 || ex > 24)) return EKF_ERANGE;
-    int rc = drain(c);
+    int rc = begin_state_write(c);
     if (rc) return rc;
     const Dims& d = c->d;
     int cb = 0;
@@ -2116,67 +1961,22 @@ extern "C" int ekf_profile_flushes(ekf_ctx* c, int cap, int* nsteps, float* ms)
 extern "C" const char* ekf_flush_kernel_name(const ekf_ctx* c, int nsteps)
 {
     if (!c || nsteps < 1) return "";
-    if (c->cfg.precision == EKF_PREC_F64) {
-        static const char* f64w[ekf::F64_WAVE_MAXS + 1] = {
-            "", "flush_f64_wave_kernel<1>", "flush_f64_wave_kernel<2>", "flush_f64_wave_kernel<3>",
-            "flush_f64_wave_kernel<4>", "flush_f64_wave_kernel<5>", "flush_f64_wave_kernel<6>",
-            "flush_f64_wave_kernel<7>", "flush_f64_wave_kernel<8>"};
-        if (nsteps <= ekf::F64_WAVE_MAXS && c->d.kmax == 16 && c->dd_variant != 2) return f64w[nsteps];
-        return "downdate_f64_kernel";
-    }
-    const bool half = c->cfg.precision == EKF_PREC_F16;
-    if (c->pmode == EKF_ARITH_F16X3 && nsteps >= 2 && nsteps <= ekf::F16X3_MAXS && nsteps % 2 == 0) {
-        struct Names {
-            char n[3][2][ekf::F16X3_MAXS / 2 + 1][64];
-            Names()
-            {
-                static const char* fmt[3] = {"flush_f32_wave_kernel<%s, %d, true, true>", "flush_bf24_kernel<%s, %d, true>",
-                                             "flush_f16q_kernel<%s, %d>"};
-                for (int f = 0; f < 3; f++)
-                    for (int h = 0; h < 2; h++)
-                        for (int k = 0; k <= ekf::F16X3_MAXS / 2; k++)
-                            snprintf(n[f][h][k], sizeof n[f][h][k], fmt[f], h ? "_Float16" : "float", 2 * k);
-            }
-        };
-        static const Names f16n;   // (initialised once, thread-safe)
-        const int form = c->dd_variant == 24 ? 1 : (c->dd_variant == 44 && nsteps >= 6 && c->nwtq > 0) ? 2 : 0;
-        return f16n.n[form][half ? 1 : 0][nsteps / 2];
-    }
-    if (c->bf && nsteps >= 2 && nsteps <= 16 && nsteps % 2 == 0 && c->dd_variant == 24) {
-        static const char* b24[2][9] = {
-            {"", "flush_bf24_kernel<float, 2>", "flush_bf24_kernel<float, 4>", "flush_bf24_kernel<float, 6>",
-             "flush_bf24_kernel<float, 8>", "flush_bf24_kernel<float, 10>", "flush_bf24_kernel<float, 12>",
-             "flush_bf24_kernel<float, 14>", "flush_bf24_kernel<float, 16>"},
-            {"", "flush_bf24_kernel<_Float16, 2>", "flush_bf24_kernel<_Float16, 4>", "flush_bf24_kernel<_Float16, 6>",
-             "flush_bf24_kernel<_Float16, 8>", "flush_bf24_kernel<_Float16, 10>", "flush_bf24_kernel<_Float16, 12>",
-             "flush_bf24_kernel<_Float16, 14>", "flush_bf24_kernel<_Float16, 16>"}};
-        return b24[half ? 1 : 0][nsteps / 2];
-    }
-    if (c->bf && nsteps >= 2 && nsteps <= 16 && nsteps % 2 == 0) {
-        static const char* bfn[2][9] = {
-            {"", "flush_f32_wave_kernel<float, 2, true>", "flush_f32_wave_kernel<float, 4, true>",
-             "flush_f32_wave_kernel<float, 6, true>", "flush_f32_wave_kernel<float, 8, true>",
-             "flush_f32_wave_kernel<float, 10, true>", "flush_f32_wave_kernel<float, 12, true>",
-             "flush_f32_wave_kernel<float, 14, true>", "flush_f32_wave_kernel<float, 16, true>"},
-            {"", "flush_f32_wave_kernel<_Float16, 2, true>", "flush_f32_wave_kernel<_Float16, 4, true>",
-             "flush_f32_wave_kernel<_Float16, 6, true>", "flush_f32_wave_kernel<_Float16, 8, true>",
-             "flush_f32_wave_kernel<_Float16, 10, true>", "flush_f32_wave_kernel<_Float16, 12, true>",
-             "flush_f32_wave_kernel<_Float16, 14, true>", "flush_f32_wave_kernel<_Float16, 16, true>"}};
-        return bfn[half ? 1 : 0][nsteps / 2];
-    }
-    const bool wave = nsteps >= 2 && nsteps <= 8 && nsteps % 2 == 0 && c->d.kmax <= 16 &&
-                      (nsteps >= 6 || c->dd_variant == 8);
-    if (wave) {
-        static const char* names[2][5] = {
-            {"", "flush_f32_wave_kernel<float, 2>", "flush_f32_wave_kernel<float, 4>",
-             "flush_f32_wave_kernel<float, 6>", "flush_f32_wave_kernel<float, 8>"},
-            {"", "flush_f32_wave_kernel<_Float16, 2>", "flush_f32_wave_kernel<_Float16, 4>",
-             "flush_f32_wave_kernel<_Float16, 6>", "flush_f32_wave_kernel<_Float16, 8>"}};
-        return names[half ? 1 : 0][nsteps / 2];
-    }
-    if (nsteps <= 4 && c->d.kmax <= 16 && c->dd_variant != 2)
-        return half ? "flush_f32_persist2_kernel<_Float16>" : "flush_f32_persist2_kernel<float>";
-    return half ? "flush_f32_sb_kernel<_Float16>" : "flush_f32_sb_kernel<float>";
+    // every name flush_plan_name can give, formatted once (the strings outlive the call)
+    constexpr int MAXS = ekf::F16X3_MAXS;   // (the largest step count a name carries)
+    struct Names {
+        char n[ekf::FLUSH_FAMILIES][2][MAXS + 1][64];
+        Names()
+        {
+            for (int f = 0; f < ekf::FLUSH_FAMILIES; f++)
+                for (int h = 0; h < 2; h++)
+                    for (int k = 0; k <= MAXS; k++)
+                        ekf::flush_plan_name(ekf::FlushPlan{(ekf::FlushFamily)f, k, h ? EKF_PREC_F16 : EKF_PREC_F32,
+                                                            ekf::GRID_STRIDED}, n[f][h][k], sizeof n[f][h][k]);
+        }
+    };
+    static const Names names;   // (initialised once, thread-safe)
+    const ekf::FlushPlan plan = flush_plan_of(c, nsteps);
+    return names.n[plan.family][plan.storage == EKF_PREC_F16][std::min(plan.nsteps, MAXS)];
 }
 
 extern "C" int ekf_debug_result_words(ekf_ctx* c, int e, int out[16])

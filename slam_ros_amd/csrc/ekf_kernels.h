@@ -6,6 +6,7 @@
 #include "../../include/slam_ekf.h"
 #include "ekf_layout.h"
 #include "ekf_commit.h"
+#include "ekf_flush_plan.h"
 
 namespace ekf {
 
@@ -70,23 +71,8 @@ struct Slot {
 };
 
 constexpr int PMAX = 32;
-constexpr int WT_R = 2, WT_C = 2, WT_N = WT_R * WT_C;   // f32 wave flush: tiles per wave-tile
-constexpr int WT64_C = 2;                                 // f64 wave flush: 1 × 2 tiles per wave-tile
-constexpr int F64_WAVE_MAXS = 8;                          // f64 wave flush: steps per launch
 constexpr int F64_RING = 4;                                // f64 wave flush: operand ring depth
-constexpr int F16X3_MAXS = 24;                            // split-fp16 contexts: flush_interval <= 24
-
-// one wave-tile of the wave flush (host-built table, read with scalar loads): the linear indices
-// of its WT_N tiles (positions below the diagonal or past the block point at a stored tile of
-// the same wave-tile and are not written back), their validity, the operand row blocks of its
-// WT_R tile rows and WT_C tile columns (16 bits each, clamped to the block) and (wr, wc)
-struct alignas(32) WtEntry {
-    int tile[WT_N];
-    int valid;      // bit i: tile i is stored
-    int rows[2];    // [0]: A row blocks (WT_R × 16 bits), [1]: B row blocks (WT_C × 16 bits)
-    int rc;         // wr | wc << 16
-};
-constexpr int DD_SB = 4;   // f32 flush: tiles per super-tile side (one wave per tile row)
+// (the flush tables' entries and tile shapes: ekf_tables.h; the flush forms' step limits: ekf_flush_plan.h)
 
 struct ScanParams {
     Dims d;
@@ -230,8 +216,7 @@ struct DowndateParams {
     Dims d;
     int E;
     int nsteps;
-    int variant;          // f32 flush form (tests only, EKF_FLUSH_VARIANT; all bit-identical): 0 auto,
-                          // 2 super-tile form, 8 wave form also for 2 or 4 steps
+    int variant;          // EKF_OPT_FLUSH_FORM (a record: the launch takes its form from the FlushPlan)
     int ncu;              // compute units (persistent grid)
     const void* Pin;
     void* Pout;
@@ -266,9 +251,10 @@ struct DowndateParams {
 hipError_t launch_scan(const ScanParams& p, int precision, hipStream_t st);
 int scan_blocks_per_cu(int precision);
 size_t scan_lds_bytes(int precision);   // static LDS of the association kernel
+// The kernel of `plan` (flush_plan: p.nsteps is the plan's); grid: the context's grid-strided size.
 // ev_a / ev_b (optional): events timestamped by the dispatch packet itself (hipExtLaunchKernelGGL),
 // so timing a flush inserts no marker packets on the stream
-hipError_t launch_downdate(const DowndateParams& p, int precision, int grid, hipStream_t st,
+hipError_t launch_downdate(const DowndateParams& p, const FlushPlan& plan, int grid, hipStream_t st,
                            hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr);
 // ex: fp16 storage exponent of the instance (ignored for f32 / f64)
 // [t0, t1): the tiles stored (t1 < 0: all); Pll points at tile t0

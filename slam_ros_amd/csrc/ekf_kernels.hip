@@ -7022,225 +7022,115 @@ hipError_t launch_scan(const ScanParams& p, int precision, hipStream_t st)
 
 #endif
 
-// The split-arithmetic flush launchers, one compilation unit each (EKF_TU 4-6: their template
-// instantiations are most of the library's device code)
-hipError_t launch_flush_bf24(const DowndateParams& p, bool half, bool f16, hipStream_t st, hipEvent_t ev_a,
-                             hipEvent_t ev_b);
-hipError_t launch_flush_f16x3(const DowndateParams& p, bool half, hipStream_t st, hipEvent_t ev_a, hipEvent_t ev_b);
-hipError_t launch_flush_bf16x6(const DowndateParams& p, bool half, hipStream_t st, hipEvent_t ev_a, hipEvent_t ev_b);
-hipError_t launch_flush_f16q(const DowndateParams& p, bool half, hipStream_t st, hipEvent_t ev_a, hipEvent_t ev_b);
+// The flush launchers. flush_plan (ekf_flush_plan.h) decides the kernel: launch_downdate switches on the
+// plan, each launcher turns its step count into the template argument. The split-arithmetic launchers
+// are one compilation unit each (EKF_TU 4-6, 9: their instantiations are most of the device code).
+static_assert(PERSIST_MAXS == PST_MAXC, "flush_plan's bound of flush_f32_persist2_kernel");
+
+// One flush launch, timed by the dispatch packet itself when ev_a / ev_b are given
+struct FlushLaunch {
+    const DowndateParams& p;
+    unsigned grid;
+    hipStream_t st;
+    hipEvent_t ev_a, ev_b;
+    template <typename K>
+    void operator()(K kernel, unsigned block = DD_THREADS) const
+    {
+        hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, ev_a, ev_b, 0, p);
+    }
+};
+
+// f(std::integral_constant<int, NS>) for the NS of LO, LO + STEP, ..., HI that equals nsteps, or an error.
+// Counts down: the innermost instantiation is emitted first, so a unit's kernels stay in ascending order
+template <int LO, int HI, int STEP, typename F>
+static hipError_t with_steps(int nsteps, F&& f)
+{
+    static_assert(HI < LO || (HI - LO) % STEP == 0, "HI is one of the steps");
+    if constexpr (HI < LO) {
+        return hipErrorInvalidValue;
+    } else {
+        if (nsteps != HI) return with_steps<LO, HI - STEP, STEP>(nsteps, f);
+        f(std::integral_constant<int, HI>{});
+        return hipGetLastError();
+    }
+}
+
+hipError_t launch_flush_bf24(const FlushLaunch& go, bool half, bool f16);
+hipError_t launch_flush_f16x3(const FlushLaunch& go, bool half);
+hipError_t launch_flush_bf16x6(const FlushLaunch& go, bool half);
+hipError_t launch_flush_f16q(const FlushLaunch& go, bool half);
 
 #if !defined(EKF_TU) || EKF_TU == 9
-hipError_t launch_flush_f16q(const DowndateParams& p, bool half, hipStream_t st, hipEvent_t ev_a, hipEvent_t ev_b)
+hipError_t launch_flush_f16q(const FlushLaunch& go, bool half)
 {
-    const unsigned wgrid = (unsigned)(8 * ((p.ncu + 7) / 8));   // one workgroup per CU
-#define EKF_F16Q_CASE(NSV)                                                                              \
-    case NSV:                                                                                           \
-        if (half) hipExtLaunchKernelGGL((flush_f16q_kernel<_Float16, NSV>), dim3(wgrid), dim3(64 * Q_WAVES), 0, st, \
-                                        ev_a, ev_b, 0, p);                                              \
-        else hipExtLaunchKernelGGL((flush_f16q_kernel<float, NSV>), dim3(wgrid), dim3(64 * Q_WAVES), 0, st, ev_a, \
-                                   ev_b, 0, p);                                                         \
-        break;
-    switch (p.nsteps) {
-        EKF_F16Q_CASE(6)
-        EKF_F16Q_CASE(8)
-        EKF_F16Q_CASE(10)
-        EKF_F16Q_CASE(12)
-        EKF_F16Q_CASE(14)
-        EKF_F16Q_CASE(16)
-        EKF_F16Q_CASE(18)
-        EKF_F16Q_CASE(20)
-        EKF_F16Q_CASE(22)
-        EKF_F16Q_CASE(24)
-        default: return hipErrorInvalidValue;
-    }
-#undef EKF_F16Q_CASE
-    return hipGetLastError();
+    return with_steps<QUAD_MINS, F16X3_MAXS, 2>(go.p.nsteps, [&](auto ns) {
+        constexpr int NS = decltype(ns)::value;
+        go(half ? flush_f16q_kernel<_Float16, NS> : flush_f16q_kernel<float, NS>, 64 * Q_WAVES);
+    });
 }
 #endif
 
 #if !defined(EKF_TU) || EKF_TU == 4
-hipError_t launch_flush_f16x3(const DowndateParams& p, bool half, hipStream_t st, hipEvent_t ev_a, hipEvent_t ev_b)
+hipError_t launch_flush_f16x3(const FlushLaunch& go, bool half)
 {
-    const unsigned wgrid = (unsigned)(8 * ((p.ncu + 7) / 8));   // one 4-wave workgroup per CU
-#define EKF_F16_CASE(NSV)                                                                               \
-case NSV:                                                                                           \
-    if (half) hipExtLaunchKernelGGL((flush_f32_wave_kernel<_Float16, NSV, true, true>), dim3(wgrid),  \
-                                    dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p);                      \
-    else hipExtLaunchKernelGGL((flush_f32_wave_kernel<float, NSV, true, true>), dim3(wgrid),          \
-                               dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p);                           \
-    break;
-    switch (p.nsteps) {
-        EKF_F16_CASE(2)
-        EKF_F16_CASE(4)
-        EKF_F16_CASE(6)
-        EKF_F16_CASE(8)
-        EKF_F16_CASE(10)
-        EKF_F16_CASE(12)
-        EKF_F16_CASE(14)
-        EKF_F16_CASE(16)
-        EKF_F16_CASE(18)
-        EKF_F16_CASE(20)
-        EKF_F16_CASE(22)
-        EKF_F16_CASE(24)
-    }
-#undef EKF_F16_CASE
-    return hipGetLastError();
+    return with_steps<2, F16X3_MAXS, 2>(go.p.nsteps, [&](auto ns) {
+        constexpr int NS = decltype(ns)::value;
+        go(half ? flush_f32_wave_kernel<_Float16, NS, true, true> : flush_f32_wave_kernel<float, NS, true, true>);
+    });
 }
 #endif
 
 #if !defined(EKF_TU) || EKF_TU == 5
-hipError_t launch_flush_bf24(const DowndateParams& p, bool half, bool f16, hipStream_t st, hipEvent_t ev_a,
-                             hipEvent_t ev_b)
+// the 2 × 4 wave-tile forms (EKF_OPT_FLUSH_FORM = 24): split-bf16 (measured 7 % slower than the
+// 2 × 2 form at T = 12; kept as an option, bit-identical) and split-fp16
+hipError_t launch_flush_bf24(const FlushLaunch& go, bool half, bool f16)
 {
-    if (!f16) {
-        // EKF_ARITH_BF16X6, EKF_FLUSH_VARIANT=24: the 2 × 4 split-bf16 wave flush (measured 7 %
-        // slower than the 2 × 2 form below at T = 12; kept as an option, bit-identical)
-        const unsigned wgrid = (unsigned)(8 * ((p.ncu + 7) / 8));   // one 4-wave workgroup per CU
-#define EKF_BF24_CASE(NSV)                                                                              \
-    case NSV:                                                                                           \
-        if (half) hipExtLaunchKernelGGL((flush_bf24_kernel<_Float16, NSV>), dim3(wgrid), dim3(DD_THREADS), 0, st, \
-                                        ev_a, ev_b, 0, p);                                              \
-        else hipExtLaunchKernelGGL((flush_bf24_kernel<float, NSV>), dim3(wgrid), dim3(DD_THREADS), 0, st, ev_a, \
-                                   ev_b, 0, p);                                                         \
-        break;
-        switch (p.nsteps) {
-            EKF_BF24_CASE(2)
-            EKF_BF24_CASE(4)
-            EKF_BF24_CASE(6)
-            EKF_BF24_CASE(8)
-            EKF_BF24_CASE(10)
-            EKF_BF24_CASE(12)
-            EKF_BF24_CASE(14)
-            EKF_BF24_CASE(16)
-        }
-#undef EKF_BF24_CASE
-        return hipGetLastError();
-        }
-        // EKF_ARITH_F16X3, EKF_OPT_FLUSH_FORM = 24: the 2 × 4 split-fp16 flush
-        const unsigned wgrid = (unsigned)(8 * ((p.ncu + 7) / 8));
-#define EKF_F24_CASE(NSV)                                                                               \
-    case NSV:                                                                                           \
-        if (half) hipExtLaunchKernelGGL((flush_bf24_kernel<_Float16, NSV, true>), dim3(wgrid), dim3(DD_THREADS), 0, st, \
-                                        ev_a, ev_b, 0, p);                                               \
-        else hipExtLaunchKernelGGL((flush_bf24_kernel<float, NSV, true>), dim3(wgrid), dim3(DD_THREADS), 0, st, ev_a, \
-                                   ev_b, 0, p);                                                          \
-        break;
-        switch (p.nsteps) {
-            EKF_F24_CASE(2)
-            EKF_F24_CASE(4)
-            EKF_F24_CASE(6)
-            EKF_F24_CASE(8)
-            EKF_F24_CASE(10)
-            EKF_F24_CASE(12)
-            EKF_F24_CASE(14)
-            EKF_F24_CASE(16)
-            EKF_F24_CASE(18)
-            EKF_F24_CASE(20)
-            EKF_F24_CASE(22)
-            EKF_F24_CASE(24)
-        }
-#undef EKF_F24_CASE
-        return hipGetLastError();
-    }
+    if (!f16)
+        return with_steps<2, BF16X6_MAXS, 2>(go.p.nsteps, [&](auto ns) {
+            constexpr int NS = decltype(ns)::value;
+            go(half ? flush_bf24_kernel<_Float16, NS> : flush_bf24_kernel<float, NS>);
+        });
+    return with_steps<2, F16X3_MAXS, 2>(go.p.nsteps, [&](auto ns) {
+        constexpr int NS = decltype(ns)::value;
+        go(half ? flush_bf24_kernel<_Float16, NS, true> : flush_bf24_kernel<float, NS, true>);
+    });
+}
 #endif
 
 #if !defined(EKF_TU) || EKF_TU == 6
-hipError_t launch_flush_bf16x6(const DowndateParams& p, bool half, hipStream_t st, hipEvent_t ev_a, hipEvent_t ev_b)
+hipError_t launch_flush_bf16x6(const FlushLaunch& go, bool half)
 {
-    const unsigned wgrid = (unsigned)(8 * ((p.ncu + 7) / 8));   // one 4-wave workgroup per CU
-#define EKF_BF_CASE(NSV)                                                                                \
-case NSV:                                                                                           \
-    if (half) hipExtLaunchKernelGGL((flush_f32_wave_kernel<_Float16, NSV, true>), dim3(wgrid), dim3(DD_THREADS), 0, \
-                                    st, ev_a, ev_b, 0, p);                                          \
-    else hipExtLaunchKernelGGL((flush_f32_wave_kernel<float, NSV, true>), dim3(wgrid), dim3(DD_THREADS), 0, st, \
-                               ev_a, ev_b, 0, p);                                                   \
-    break;
-    switch (p.nsteps) {
-        EKF_BF_CASE(2)
-        EKF_BF_CASE(4)
-        EKF_BF_CASE(6)
-        EKF_BF_CASE(8)
-        EKF_BF_CASE(10)
-        EKF_BF_CASE(12)
-        EKF_BF_CASE(14)
-        EKF_BF_CASE(16)
-    }
-#undef EKF_BF_CASE
-    return hipGetLastError();
+    return with_steps<2, BF16X6_MAXS, 2>(go.p.nsteps, [&](auto ns) {
+        constexpr int NS = decltype(ns)::value;
+        go(half ? flush_f32_wave_kernel<_Float16, NS, true> : flush_f32_wave_kernel<float, NS, true>);
+    });
 }
 #endif
 
 #if !defined(EKF_TU) || EKF_TU == 2
-hipError_t launch_downdate(const DowndateParams& p, int precision, int grid, hipStream_t st, hipEvent_t ev_a,
+hipError_t launch_downdate(const DowndateParams& p, const FlushPlan& plan, int grid, hipStream_t st, hipEvent_t ev_a,
                            hipEvent_t ev_b)
 {
-    if (precision == EKF_PREC_F64) {
-        if (p.nsteps <= F64_WAVE_MAXS && p.d.kmax == 16 && p.nwt64 > 0 && p.wt64 != nullptr && p.variant != 2) {
-            const unsigned wgrid = (unsigned)(8 * ((p.ncu + 7) / 8));   // one 4-wave workgroup per CU
-            switch (p.nsteps) {
-            case 1: hipExtLaunchKernelGGL((flush_f64_wave_kernel<1>), dim3(wgrid), dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p); break;
-            case 2: hipExtLaunchKernelGGL((flush_f64_wave_kernel<2>), dim3(wgrid), dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p); break;
-            case 3: hipExtLaunchKernelGGL((flush_f64_wave_kernel<3>), dim3(wgrid), dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p); break;
-            case 4: hipExtLaunchKernelGGL((flush_f64_wave_kernel<4>), dim3(wgrid), dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p); break;
-            case 5: hipExtLaunchKernelGGL((flush_f64_wave_kernel<5>), dim3(wgrid), dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p); break;
-            case 6: hipExtLaunchKernelGGL((flush_f64_wave_kernel<6>), dim3(wgrid), dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p); break;
-            case 7: hipExtLaunchKernelGGL((flush_f64_wave_kernel<7>), dim3(wgrid), dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p); break;
-            default: hipExtLaunchKernelGGL((flush_f64_wave_kernel<8>), dim3(wgrid), dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p); break;
-            }
-            return hipGetLastError();
-        }
-        hipExtLaunchKernelGGL(downdate_f64_kernel, dim3(grid), dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p);
-        return hipGetLastError();
-    }
-    const bool half = precision == EKF_PREC_F16;
-    // default: the wave flush for groups of 6 or 8 steps; EKF_FLUSH_VARIANT 8 forces it (also
-    // for 2 or 4 steps)
-    const bool wave_shape = p.nsteps >= 2 && p.nsteps <= 8 && p.nsteps % 2 == 0 && p.d.kmax <= 16 &&
-                            p.nwt > 0 && p.wt != nullptr;
-    const bool wave_ok = wave_shape && (p.nsteps >= 6 || p.variant == 8);
-    const bool bf_shape = p.nsteps >= 2 && p.nsteps <= (p.bf == 2 ? F16X3_MAXS : 16) && p.nsteps % 2 == 0 && p.d.kmax <= 16 &&
-                          p.nwt > 0 && p.wt != nullptr;
-    if (p.bf == 1 && bf_shape && p.variant == 24 && p.nwt24 > 0 && p.wt24 != nullptr)
-        return launch_flush_bf24(p, half, false, st, ev_a, ev_b);
-    if (p.bf == 2 && bf_shape && p.variant == 24 && p.nwt24 > 0 && p.wt24 != nullptr)
-        return launch_flush_bf24(p, half, true, st, ev_a, ev_b);
-    if (p.bf == 2 && bf_shape && p.variant == 44 && p.nsteps >= 6 && p.nwtq > 0 && p.wtq != nullptr)
-        return launch_flush_f16q(p, half, st, ev_a, ev_b);   // the quad form (groups of 6-24 steps)
-    if (p.bf == 2 && bf_shape)   // EKF_ARITH_F16X3: split-fp16 wave flush, groups of 2-24 steps (even)
-        return launch_flush_f16x3(p, half, st, ev_a, ev_b);
-    if (p.bf == 1 && bf_shape)   // EKF_ARITH_BF16X6: split-bf16 wave flush, groups of 2-16 steps (even)
-        return launch_flush_bf16x6(p, half, st, ev_a, ev_b);
-    if (wave_ok) {
-        const unsigned wgrid = (unsigned)(8 * ((p.ncu + 7) / 8));   // one 4-wave workgroup per CU
-#define EKF_WAVE_CASE(NSV)                                                                              \
-    case NSV:                                                                                           \
-        if (half) hipExtLaunchKernelGGL((flush_f32_wave_kernel<_Float16, NSV>), dim3(wgrid), dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p); \
-        else hipExtLaunchKernelGGL((flush_f32_wave_kernel<float, NSV>), dim3(wgrid), dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p);         \
-        break;
-        switch (p.nsteps) {
-            EKF_WAVE_CASE(2)
-            EKF_WAVE_CASE(4)
-            EKF_WAVE_CASE(6)
-            EKF_WAVE_CASE(8)
-        }
-#undef EKF_WAVE_CASE
-        return hipGetLastError();
-    }
-    if (p.nsteps <= PST_MAXC && p.d.kmax <= 16 && p.variant != 2) {
-        const int pgrid = 16 * ((p.ncu + 7) / 8);   // two workgroups per CU (48 KB LDS each)
-        if (half)
-            hipExtLaunchKernelGGL(flush_f32_persist2_kernel<_Float16>, dim3((unsigned)pgrid), dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p);
-        else
-            hipExtLaunchKernelGGL(flush_f32_persist2_kernel<float>, dim3((unsigned)pgrid), dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p);
-    } else {
-        const int64_t nsb = (p.d.nb + DD_SB - 1) / DD_SB;
-        const int64_t total = (int64_t)p.E * (nsb * (nsb + 1) / 2);
-        const unsigned sgrid = (unsigned)(8 * ((total + 7) / 8));
-        if (half)
-            hipExtLaunchKernelGGL(flush_f32_sb_kernel<_Float16>, dim3(sgrid), dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p);
-        else
-            hipExtLaunchKernelGGL(flush_f32_sb_kernel<float>, dim3(sgrid), dim3(DD_THREADS), 0, st, ev_a, ev_b, 0, p);
+    if (p.nsteps != plan.nsteps) return hipErrorInvalidValue;
+    const bool half = plan.storage == EKF_PREC_F16;
+    const FlushLaunch go{p, flush_grid_size(plan.grid, p.ncu, grid, p.E, p.d.nb), st, ev_a, ev_b};
+    switch (plan.family) {
+    case FLUSH_F64_WAVE:
+        return with_steps<1, F64_WAVE_MAXS, 1>(p.nsteps, [&](auto ns) { go(flush_f64_wave_kernel<decltype(ns)::value>); });
+    case FLUSH_F64_TILE: go(downdate_f64_kernel); break;
+    case FLUSH_BF16_2X4: return launch_flush_bf24(go, half, false);
+    case FLUSH_F16_2X4: return launch_flush_bf24(go, half, true);
+    case FLUSH_F16_QUAD: return launch_flush_f16q(go, half);
+    case FLUSH_F16_WAVE: return launch_flush_f16x3(go, half);
+    case FLUSH_BF16_WAVE: return launch_flush_bf16x6(go, half);
+    case FLUSH_F32_WAVE:
+        return with_steps<2, F32_WAVE_MAXS, 2>(p.nsteps, [&](auto ns) {
+            constexpr int NS = decltype(ns)::value;
+            go(half ? flush_f32_wave_kernel<_Float16, NS> : flush_f32_wave_kernel<float, NS>);
+        });
+    case FLUSH_F32_PERSIST: go(half ? flush_f32_persist2_kernel<_Float16> : flush_f32_persist2_kernel<float>); break;
+    case FLUSH_F32_SUPERTILE: go(half ? flush_f32_sb_kernel<_Float16> : flush_f32_sb_kernel<float>); break;
+    default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

@@ -158,7 +158,9 @@ def test_one_call_scan_in_process(ekf_mod, oracle_mod):
     checks (no communicator attached: EKF_EINVAL; a rank or world other than the context's:
     EKF_EINVAL; more lines than the context takes: EKF_ERANGE), then a world of one attached to
     the library's own RCCL communicator, its scans against one context of the same library
-    (bit-identical state and associations) and the restatement (associations)."""
+    (bit-identical state and associations) and the restatement (associations). The partitioned
+    context is drained after scan 5, so it flushes groups of 4, 1 and 1 steps: an odd group runs the
+    wave kernel on one step more (a step that applies nothing), and flush_kernel_name says so."""
     import ctypes
     N, T, scans = 512, 4, 6
     lib = ekf_mod.load_library()
@@ -181,6 +183,7 @@ def test_one_call_scan_in_process(ekf_mod, oracle_mod):
     assert lib.ekf_shard_attach_rccl(sh.handle, uid, 1, 1) == 1   # rank outside the context's world
     assert lib.ekf_shard_attach_rccl(sh.handle, uid, 0, 2) == 1   # not the context's world
     assert lib.ekf_shard_attach_rccl(sh.handle, uid, 0, 1) == 0
+    sh.profile(1)
     big = np.zeros((9, 6))
     assert lib.ekf_shard_localize(sh.handle, dp(enc0), dp(big), 9, ctypes.byref(res)) == 4   # ERANGE
     for step in range(1, scans + 1):
@@ -192,8 +195,14 @@ def test_one_call_scan_in_process(ekf_mod, oracle_mod):
         m = list(res[0].match[: res[0].nlines])
         assert m == list(r1["match"][: len(ln)]), step
         assert ref.localize(ln, enc[0]) == m, step
+        if step == 5:
+            sh.sync()
     P1, y1, s1, p1 = one.download_state(0)
     P2, y2, s2, p2 = sh.download_state(0)
+    assert [n for n, _ in sh.profile_flushes()] == [4, 1, 1]
+    assert sh.flush_kernel_name(1) == "flush_f32_wave_kernel<float, 2>"
+    assert sh.flush_kernel_name(3) == "flush_f32_wave_kernel<float, 4>"
+    assert sh.flush_kernel_name(4) == "flush_f32_wave_kernel<float, 4>"
     np.testing.assert_array_equal(P2, P1)
     np.testing.assert_array_equal(y2, y1)
     assert s1 == s2
