@@ -18,8 +18,6 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libslam_ekf.so")
-SOURCES = ["ekf_kernels.hip", "ekf_api.hip"]
-HEADERS = ["ekf_kernels.h", "ekf_layout.h", "ekf_commit.h", "ekf_flush_plan.h", "ekf_tables.h"]
 ARCH = "gfx950"
 
 
@@ -80,23 +78,30 @@ def last_build() -> dict:
 # step on the VALU, which cannot read AGPRs, so the AGPR form paid a read + write copy per
 # element per step (fp16 flush 0.84 -> 0.72 ms at N=4096, T=8; fp32 unchanged or faster)
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-mllvm", "-amdgpu-mfma-vgpr-form"]
-# ekf_kernels.hip is compiled as nine units (EKF_TU: 1 association kernels, 2 the exact and fp64
-# flushes, 3 the rest, 4 / 5 / 6 the split-fp16, 2 x 4 and split-bf16 flushes, 7 / 8 the association
-# kernel on 128 / 64 landmarks per workgroup, 9 the split-fp16 quad flush), in parallel with ekf_api.hip: each unit instantiates
-# only the kernels its launchers use
-UNITS = [("ekf_kernels.hip", 4), ("ekf_kernels.hip", 2), ("ekf_kernels.hip", 1), ("ekf_kernels.hip", 7),
-         ("ekf_kernels.hip", 8), ("ekf_kernels.hip", 5), ("ekf_kernels.hip", 6), ("ekf_kernels.hip", 3), ("ekf_kernels.hip", 9),
-         ("ekf_api.hip", 0)]
+# The compilation units, in link order (the order of the code objects in the library). Each
+# unit_*.hip includes the device code its kernels need (the flush units a header per flush family,
+# the others the association kernels, ekf_kernels.hip, which is not compiled on its own) and defines
+# the launchers that instantiate them; they compile in parallel with ekf_api.hip.
+UNITS = ["unit_flush_f16x3.hip", "unit_flush_exact.hip", "unit_scan.hip", "unit_scan_nt128.hip",
+         "unit_scan_nt64.hip", "unit_flush_2x4.hip", "unit_flush_bf16x6.hip", "unit_shard_pack.hip",
+         "unit_flush_quad.hip", "ekf_api.hip"]
+
+
+def source_deps(csrc: str = CSRC) -> list[str]:
+    """What the library is built from: every .hip and .h under csrc/, the public header, this file."""
+    files = sorted(os.path.join(base, f) for base, _dirs, names in os.walk(csrc)
+                   for f in names if f.endswith((".hip", ".h")))
+    return files + [os.path.join(ROOT, "include", "slam_ekf.h"), os.path.abspath(__file__)]
 
 
 def _compile_link(out: str, defines: list[str], verbose: bool = False, csrc: str = CSRC) -> None:
     objdir = out + ".objs"
     os.makedirs(objdir, exist_ok=True)
     procs, objs = [], []
-    for src, tu in UNITS:
-        obj = os.path.join(objdir, f"{os.path.splitext(src)[0]}_{tu}.o")
+    for src in UNITS:
+        obj = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
         cmd = [hipcc(), f"--offload-arch={ARCH}", *FLAGS, *[f"-D{d}" for d in defines],
-               *([f"-DEKF_TU={tu}"] if tu else []), "-c", os.path.join(csrc, src), "-o", obj]
+               "-c", os.path.join(csrc, src), "-o", obj]
         if verbose:
             print(" ".join(cmd))
         procs.append(subprocess.Popen(cmd))
@@ -117,10 +122,7 @@ def build_variant(out: str, defines: list[str], csrc: str = CSRC) -> str:
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS]
-    deps.append(os.path.join(ROOT, "include", "slam_ekf.h"))
-    deps.append(os.path.abspath(__file__))   # compile flags live here
-    src = _sha(deps)
+    src = _sha(source_deps())   # (this file among them: the compile flags live here)
     rec = _record()
     reuse = (not force and os.path.exists(LIB_PATH) and rec.get("source_sha") == src
              and rec.get("lib_sha") == _file_sha(LIB_PATH))

@@ -1,4 +1,4 @@
-// ekf_api.hip — C-ABI (include/slam_ekf.h) over the gfx950 kernels in ekf_kernels.hip.
+// ekf_api.hip — C-ABI (include/slam_ekf.h) over the gfx950 kernels (launchers: unit_*.hip).
 //
 // A context owns E instances' state in HBM and two HIP streams:
 //   S  association/gain kernels (scan_kernel) — all state except the landmark block — and, on
@@ -7,7 +7,7 @@
 // Every update step k writes its downdate operands, augmented rows and result record into slot
 // k mod R of a ring. The landmark block is rewritten by a flush once per group of T =
 // flush_interval steps; association kernels read the last materialised block ("base") with the
-// steps not yet in it applied on read (bit-identical to flushing first, see ekf_kernels.hip).
+// steps not yet in it applied on read (bit-identical to flushing first, see ekf_device.h).
 //   sequential (pipeline = 0): one buffer, flushed in place on S after the group's last scan;
 //     R = T.
 //   pipelined  (pipeline = 1): flush f reads X[in] and writes X[out] = the other buffer while the

@@ -1,4 +1,4 @@
-// ekf_kernels.h — launch parameters shared by ekf_kernels.hip and ekf_api.hip.
+// ekf_kernels.h — launch parameters and launchers shared by the kernels' units (unit_*.hip) and ekf_api.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>

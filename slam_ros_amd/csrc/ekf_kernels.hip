@@ -1,520 +1,15 @@
-// ekf_kernels.hip — gfx950 kernels of the EKF-SLAM update (slam_ros Robot::localize).
-//
-// Per scan (one "step"), all E ensemble instances at once:
-//   1. scan_kernel (⌈N/256⌉ cooperating 256-thread workgroups per instance, stream S)
-//        predict of the robot strip (Robot.cpp:130-286: Fx = I outside rows 0..2), then for
-//        every observed line in order: Mahalanobis gating of all unmatched saved landmarks in
-//        parallel + min-index reduction (== the reference's first passing candidate,
-//        Robot.cpp:313-504); for a match the gain chain in deferred low-rank form
-//        (Robot.cpp:515-602): W_t = P_{t-1}·H_tᵀ, K_t = W_t·S_t⁻¹, U_t = K_t·S_t, y += K_t·v_t.
-//        Landmark augmentation (Robot.cpp:776-866) and the capacity reset decision
-//        (Robot.cpp:893-904) run at the end of the same kernel; the new landmarks' rows of the
-//        landmark block go to the step's slot (patch buffers), the rank-2m operands U/V to the
-//        slot's MFMA-ordered operand buffers.
-//   2. flush (stream S; D when pipelined): one pass over the packed landmark block applying a
-//        group of T steps in order — per step X ← X − U_t·V_tᵀ (rank 2m on MFMA, the reference's
-//        m dense n×n passes of Robot.cpp:560-572 fused), then that step's augmented rows, or the
-//        reset. Each stored tile is read and written once per group. fp32/fp16 storage:
-//        flush_f32_wave_kernel (groups of 6-8 steps: barrier-free waves, one wave-tile of
-//        prefetch), flush_f32_persist2_kernel (≤ 4 steps, LDS-staged super-tiles),
-//        flush_f32_sb_kernel (otherwise); fp64: downdate_f64_kernel (one tile per wave).
-//
-// Deferred reads: between flushes the association kernels read the landmark block with the
-// pending steps applied on read (pll_block): per element, the same k-ordered fp32/fp64 FMA chain
-// the MFMA executes, then the patch rounded to storage, so every read sees bit-for-bit the value
-// the flush will store (tests/test_gpu_parity.py::test_deferred_flush_equals_drained).
-#include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
-
-#include <type_traits>
-
-#include "ekf_kernels.h"
-
-namespace ekf {
-
-#define EKF_PI 3.14159265358979323846
-
-
-// Storage type T of the landmark block → compute type C (MFMA / FMA chain) and tile layout L.
-// fp16 storage computes in fp32 on the f32 layout and rounds to fp16 after every step, in the
-// flush and in the on-read replay alike, so the stored value never depends on when it is flushed.
-// It holds 2^x·P with a per-instance exponent x (ScanParams/DowndateParams::pexp, default 10:
-// |P| < 64 representable, normal down to 6e-8; chosen at upload from the largest landmark
-// variance, ekf_api.hip choose_exponent). The fp16 path computes in that scaled domain
-// throughout: the scan writes the U operand scaled by 2^x (exact), so flush and on-read replay
-// both run acc = 2^x·X − (2^x·U)·Vᵀ, bit-for-bit 2^x × the unscaled chain, and round with two
-// conversions per element; values leave the scaled domain only where they are read as P.
-template <typename T> struct Stor {
-    using C = T;
-    using L = T;
-    static constexpr bool half = false;
-};
-template <> struct Stor<_Float16> {
-    using C = float;
-    using L = float;
-    static constexpr bool half = true;
-};
-
-template <typename T>
-__device__ __forceinline__ T to_store(typename Stor<T>::C x)
-{
-    return (T)x;
-}
-
-template <typename T>
-__device__ __forceinline__ typename Stor<T>::C from_store(T h)
-{
-    return (typename Stor<T>::C)h;
-}
-
-template <typename T>
-__device__ __forceinline__ typename Stor<T>::C round_step(typename Stor<T>::C x)
-{
-    if constexpr (Stor<T>::half) {
-        // the same instruction on every path: the compiler may otherwise pair two roundings into
-        // v_cvt_pk_f16_f32 at some call sites, which does not round fp16 subnormals like
-        // v_cvt_f16_f32 (the flush and the on-read replay must round bit-identically)
-        float r;
-        asm("v_cvt_f16_f32 %0, %1\n\tv_cvt_f32_f16 %0, %0" : "=v"(r) : "v"(x));
-        return r;
-    } else {
-        return (typename Stor<T>::C)(T)x;
-    }
-}
-
-// P value (fp64) → scaled compute domain (exponent ex, fp16 storage only), and back: power-of-two
-// scalings, exact in fp32 / fp64
-template <typename T>
-__device__ __forceinline__ typename Stor<T>::C to_domain(double v, int ex)
-{
-    using C = typename Stor<T>::C;
-    if constexpr (Stor<T>::half) return ldexpf((C)v, ex);
-    else return (C)v;
-}
-
-template <typename T>
-__device__ __forceinline__ double from_domain(typename Stor<T>::C x, int ex)
-{
-    if constexpr (Stor<T>::half) return ldexp((double)x, -ex);
-    else return (double)x;
-}
-
-// the storage exponent of instance e (0 unless fp16)
-template <typename T>
-__device__ __forceinline__ int storage_exp(const int* pexp, int e);
-
-// A flush's U operand rows of instance e: as stored, or (DowndateParams::usym: symmetric operands,
-// U = −2^x·V exactly) the V rows times us_of(). Either way the same fp32 values reach the MFMAs.
-template <typename TS>
-__device__ __forceinline__ float us_of(const DowndateParams& p, int e)
-{
-    return p.usym ? -ldexpf(1.0f, storage_exp<TS>(p.pexp, e)) : 1.0f;
-}
-__device__ __forceinline__ const float* u_rows_flush(const DowndateParams& p, const Slot& sq, int e, size_t opstride)
-{
-    return reinterpret_cast<const float*>(p.usym ? sq.Vop : sq.Uop) + e * opstride;
-}
-
-template <typename T>
-__device__ __forceinline__ int storage_exp(const int* pexp, int e)
-{
-    if constexpr (Stor<T>::half) return pexp[e];
-    else return 0;
-}
-
-__device__ __forceinline__ double normalize_radian(double rad)
-{
-    // Robot.cpp:62-71
-    if (fabs(rad) <= EKF_PI) return rad;   // (the common case, one test)
-    if (rad > EKF_PI) {
-        rad = rad - (2.0 * EKF_PI + floor(rad / (2.0 * EKF_PI)) * 2.0 * EKF_PI);
-    } else if (rad < -EKF_PI) {
-        rad = rad + (2.0 * EKF_PI + floor(fabs(rad) / (2.0 * EKF_PI)) * 2.0 * EKF_PI);
-    }
-    return rad;
-}
-
-// 1/a for a finite nonzero a of moderate exponent: v_rcp_f64 and two Newton steps (within an ulp;
-// the association chain's divisions, which sit on its critical path, take this instead of the
-// correctly rounded division)
-__device__ __forceinline__ double rcp_nr(double a)
-{
-    double r = __builtin_amdgcn_rcp(a);
-    double e = fma(-a, r, 1.0);
-    r = fma(r, e, r);
-    e = fma(-a, r, 1.0);
-    return fma(r, e, r);
-}
-
-// gsl_linalg_LU_decomp + LU_invert on 2x2 (Robot.cpp:449-457): partial pivoting, the elimination
-// and the two back substitutions of GSL, with the pivots' reciprocals (rcp_nr) in place of the
-// divisions (agrees with GSL within an ulp or two per entry); false when U is singular (GSL_EDOM),
-// leaving Si untouched.
-__device__ __forceinline__ bool lu_invert2(const double S[4], double Si[4])
-{
-    // the row swap by selects and the elimination unconditionally (a zero pivot makes r0 infinite,
-    // and the function then returns before using anything derived from it): the same values as
-    // the branching form, without exec-mask branches on the association's serial chain
-    const bool sw = fabs(S[2]) > fabs(S[0]);
-    double a0 = sw ? S[2] : S[0], a1 = sw ? S[3] : S[1], a2 = sw ? S[0] : S[2], a3 = sw ? S[1] : S[3];
-    const int p0 = sw ? 1 : 0, p1 = sw ? 0 : 1;
-    const double r0 = rcp_nr(a0);
-    const double l = a2 * r0;
-    a2 = l;
-    a3 -= l * a1;
-    if (a0 == 0.0 || a3 == 0.0) return false;
-    const double r3 = rcp_nr(a3);
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        double b0 = (p0 == c) ? 1.0 : 0.0;
-        double b1 = (p1 == c) ? 1.0 : 0.0;
-        b1 = b1 - a2 * b0;
-        const double x1 = b1 * r3;
-        const double x0 = (b0 - a1 * x1) * r0;
-        Si[c] = x0;
-        Si[2 + c] = x1;
-    }
-    return true;
-}
-
-// ---------------------------------------------------------------------------------------
-// Landmark block as seen by a step: X plus the pending (not yet flushed) steps, in order.
-// ---------------------------------------------------------------------------------------
-template <typename T>
-struct PllView {
-    const T* X;
-    int nb, kmax, M, max_lines;
-    int e;            // instance
-    int ex;           // storage exponent of instance e (fp16)
-    size_t opstride;  // operand elements per instance
-    int npend;        // pending steps (oldest first)
-    const Slot* pend;
-    const int4* ctl;  // per pending step {reset, ks, nadd, s0} of instance e (LDS copy)
-    int rnd;          // fp16: round after every pending step, as the exact flush does (0 under
-                      // the split-bf16 flush, which rounds once per group)
-    int usym;         // symmetric operands: U = us·V, the U rows not stored (ScanParams::usym)
-    float us;         // −2^ex if usym, else 1 (U rows read as stored)
-};
-
-// Step q's U rows as stored, or its V rows (scaled by v.us on use) for symmetric operands
-template <typename T>
-__device__ __forceinline__ const float* u_rows_f32(const PllView<T>& v, const Slot& sq)
-{
-    return reinterpret_cast<const float*>(v.usym ? sq.Vop : sq.Uop) + v.e * v.opstride;
-}
-
-// fp16 rounding of a replayed element (identity for fp32 / fp64 storage)
-template <typename T>
-__device__ __forceinline__ typename Stor<T>::C vround(const PllView<T>& v, typename Stor<T>::C x)
-{
-    return v.rnd ? round_step<T>(x) : x;
-}
-
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-
-// Staged rows of a guessed column (LDS, per column and pending step: [U | V][row half][8]):
-// the U side as in the operand layout, row half rh = (k parity) · 2 + (row of the pair), 8 k each;
-// the V side interleaved by row pair, (rh, k) at (rh >> 1) · 16 + 2k + (rh & 1), so that one
-// float2 holds both rows of a k (a packed-FMA operand).
-__device__ __forceinline__ int stage_v_index(int rh, int k) { return (rh >> 1) * 16 + 2 * k + (rh & 1); }
-
-// EKF_ARITH_BF16X6: v = hi + mid + lo, each a bf16 (the upper half of an fp32): truncation leaves
-// an exact fp32 remainder of at most 16, then 8 significant bits, so the three parts are exact.
-// Packs (a, b) into one dword per part, a in the low half (operand element order)
-__device__ __forceinline__ void split_pack(float a, float b, unsigned (&o)[3])
-{
-#pragma unroll
-    for (int pl = 0; pl < 3; pl++) {
-        const unsigned ua = __builtin_bit_cast(unsigned, a) & 0xffff0000u;
-        const unsigned ub = __builtin_bit_cast(unsigned, b) & 0xffff0000u;
-        o[pl] = (ua >> 16) | ub;
-        a -= __builtin_bit_cast(float, ua);
-        b -= __builtin_bit_cast(float, ub);
-    }
-}
-
-// Stored 2×2 block at rows a0, a0+1 and columns b0, b0+1 (a0, b0 even, a0's tile <= b0's):
-// acc = {(a0,b0), (a0,b0+1), (a0+1,b0), (a0+1,b0+1)}. In the f32 tile layout the two rows of a
-// column are adjacent and the two columns are 4 elements apart: two paired loads.
-template <typename T>
-__device__ __forceinline__ void load_block(const PllView<T>& v, int a0, int b0, typename Stor<T>::C (&acc)[4])
-{
-    using L = typename Stor<T>::L;
-    if constexpr (sizeof(L) == 4) {
-        const T* x = v.X + ll_offset<L>(a0, b0, v.nb);
-        if constexpr (sizeof(T) == 4) {
-            const float2 c0 = *reinterpret_cast<const float2*>(x);
-            const float2 c1 = *reinterpret_cast<const float2*>(x + 4);
-            acc[0] = from_store<T>(c0.x); acc[2] = from_store<T>(c0.y);
-            acc[1] = from_store<T>(c1.x); acc[3] = from_store<T>(c1.y);
-        } else {
-            typedef T t2 __attribute__((ext_vector_type(2)));
-            const t2 c0 = *reinterpret_cast<const t2*>(x);
-            const t2 c1 = *reinterpret_cast<const t2*>(x + 4);
-            acc[0] = from_store<T>(c0.x); acc[2] = from_store<T>(c0.y);
-            acc[1] = from_store<T>(c1.x); acc[3] = from_store<T>(c1.y);
-        }
-    } else {
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-            for (int c = 0; c < 2; c++) acc[p * 2 + c] = from_store<T>(v.X[ll_offset<L>(a0 + p, b0 + c, v.nb)]);
-    }
-}
-
-// The rows a step appended (Robot.cpp:845-862) replace block (i0, j0) if it lies in them:
-// requested orientation, rounded as they are stored.
-template <typename T>
-__device__ __forceinline__ void patch_block(const PllView<T>& v, const Slot& sq, int4 cw, int i0, int j0,
-                                            bool swap, typename Stor<T>::C (&acc)[4])
-{
-    const int nadd = cw.z, s0 = cw.w;
-    const int li = i0 >> 1, lj = j0 >> 1;
-    const int hi = li > lj ? li : lj;
-    if (hi >= s0 && hi < s0 + nadd) {
-        const int qa = hi - s0;
-        const double* pdg = sq.patch_diag + (size_t)v.e * v.max_lines * 4;
-        const double* prw = sq.patch + ((size_t)v.e * v.max_lines + qa) * 2 * v.M;
-        double raw[4];
-        if (li == lj) {
-            raw[0] = pdg[qa * 4 + 0]; raw[1] = pdg[qa * 4 + 1];
-            raw[2] = pdg[qa * 4 + 2]; raw[3] = pdg[qa * 4 + 3];
-        } else if (li > lj) {
-            raw[0] = prw[j0]; raw[1] = prw[j0 + 1];
-            raw[2] = prw[v.M + j0]; raw[3] = prw[v.M + j0 + 1];
-        } else {
-            raw[0] = prw[i0]; raw[1] = prw[v.M + i0];
-            raw[2] = prw[i0 + 1]; raw[3] = prw[v.M + i0 + 1];
-        }
-        if (swap) {
-            acc[0] = vround<T>(v, to_domain<T>(raw[0], v.ex)); acc[1] = vround<T>(v, to_domain<T>(raw[2], v.ex));
-            acc[2] = vround<T>(v, to_domain<T>(raw[1], v.ex)); acc[3] = vround<T>(v, to_domain<T>(raw[3], v.ex));
-        } else {
-            acc[0] = vround<T>(v, to_domain<T>(raw[0], v.ex)); acc[1] = vround<T>(v, to_domain<T>(raw[1], v.ex));
-            acc[2] = vround<T>(v, to_domain<T>(raw[2], v.ex)); acc[3] = vround<T>(v, to_domain<T>(raw[3], v.ex));
-        }
-    }
-}
-
-// One pending step's downdate on B blocks (i0, j0[b]) in their stored orientations (pll_blocks):
-// the owned rows i0, i0+1 of U and V are loaded once per k-chunk (their lanes' addresses are
-// spread over many cache lines) and each column landmark's rows once (U_col for a transposed
-// block, V_col otherwise; the guessed columns are the same for the whole wave). Per element the
-// FMA chain of pll_blocks' per-block form, operand for operand.
-template <typename T, int B>
-__device__ __forceinline__ void pll_shared_step(const PllView<T>& v, const Slot& sq, int ks, int i0,
-                                                const int (&j0)[B], const bool (&swap)[B],
-                                                typename Stor<T>::C (&acc)[B][4])
-{
-    using C = typename Stor<T>::C;
-    if constexpr (sizeof(C) == 4) {
-        const int kh = v.kmax / 2;
-        const float* U = u_rows_f32(v, sq);
-        const float* V = reinterpret_cast<const float*>(sq.Vop) + v.e * v.opstride;
-        const float us = v.us;
-        auto row = [&](int r) { return ((size_t)(r >> 5) * 64 + (r & 31)) * kh; };
-        const float* uo = U + row(i0);
-        const float* vo = V + row(i0);
-        const float* xc[B];
-#pragma unroll
-        for (int b = 0; b < B; b++) xc[b] = (swap[b] ? U : V) + row(j0[b]);
-        for (int s0 = 0; s0 < ks; s0 += 4) {
-            // [row, row + 1] × [k half 0, k half 1] of the owned U and V rows
-            const f32x4v ue0 = *reinterpret_cast<const f32x4v*>(uo + s0) * us;
-            const f32x4v ue1 = *reinterpret_cast<const f32x4v*>(uo + kh + s0) * us;
-            const f32x4v uo0 = *reinterpret_cast<const f32x4v*>(uo + 32 * kh + s0) * us;
-            const f32x4v uo1 = *reinterpret_cast<const f32x4v*>(uo + 33 * kh + s0) * us;
-            const f32x4v ve0 = *reinterpret_cast<const f32x4v*>(vo + s0);
-            const f32x4v ve1 = *reinterpret_cast<const f32x4v*>(vo + kh + s0);
-            const f32x4v vo0 = *reinterpret_cast<const f32x4v*>(vo + 32 * kh + s0);
-            const f32x4v vo1 = *reinterpret_cast<const f32x4v*>(vo + 33 * kh + s0);
-#pragma unroll
-            for (int b = 0; b < B; b++) {
-                const f32x4v ce0 = *reinterpret_cast<const f32x4v*>(xc[b] + s0);
-                const f32x4v ce1 = *reinterpret_cast<const f32x4v*>(xc[b] + kh + s0);
-                const f32x4v co0 = *reinterpret_cast<const f32x4v*>(xc[b] + 32 * kh + s0);
-                const f32x4v co1 = *reinterpret_cast<const f32x4v*>(xc[b] + 33 * kh + s0);
-                const bool sw = swap[b];
-                const f32x4v ae0 = sw ? ce0 * us : ue0, ae1 = sw ? ce1 * us : ue1, ao0 = sw ? co0 * us : uo0,
-                             ao1 = sw ? co1 * us : uo1;
-                const f32x4v be0 = sw ? ve0 : ce0, be1 = sw ? ve1 : ce1, bo0 = sw ? vo0 : co0, bo1 = sw ? vo1 : co1;
-#pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    if (s0 + s >= ks) break;
-                    acc[b][0] = fmaf(ao0[s], bo0[s], fmaf(ae0[s], be0[s], acc[b][0]));
-                    acc[b][1] = fmaf(ao0[s], bo1[s], fmaf(ae0[s], be1[s], acc[b][1]));
-                    acc[b][2] = fmaf(ao1[s], bo0[s], fmaf(ae1[s], be0[s], acc[b][2]));
-                    acc[b][3] = fmaf(ao1[s], bo1[s], fmaf(ae1[s], be1[s], acc[b][3]));
-                }
-            }
-        }
-    } else {
-        const int kq = v.kmax / 4;
-        const double* U = reinterpret_cast<const double*>(sq.Uop) + v.e * v.opstride;
-        const double* V = reinterpret_cast<const double*>(sq.Vop) + v.e * v.opstride;
-        auto row = [&](int r) { return ((size_t)(r >> 5) * 64 + (r & 15)) * (2 * kq) + ((r >> 4) & 1) * kq; };
-        const double* uo = U + row(i0);
-        const double* vo = V + row(i0);
-        const double* xc[B];
-#pragma unroll
-        for (int b = 0; b < B; b++) xc[b] = (swap[b] ? U : V) + row(j0[b]);
-        for (int s = 0; s < ks; s++)
-#pragma unroll
-            for (int kk = 0; kk < 4; kk++) {
-                const size_t o = (size_t)16 * kk * 2 * kq + s;
-                const double u0 = uo[o], u1 = uo[o + 2 * kq];
-                const double w0 = vo[o], w1 = vo[o + 2 * kq];
-#pragma unroll
-                for (int b = 0; b < B; b++) {
-                    const double c0 = xc[b][o], c1 = xc[b][o + 2 * kq];
-                    const bool sw = swap[b];
-                    const double x0 = sw ? c0 : u0, x1 = sw ? c1 : u1;
-                    const double y0 = sw ? w0 : c0, y1 = sw ? w1 : c1;
-                    acc[b][0] = fma(x0, y0, (double)acc[b][0]);
-                    acc[b][1] = fma(x0, y1, (double)acc[b][1]);
-                    acc[b][2] = fma(x1, y0, (double)acc[b][2]);
-                    acc[b][3] = fma(x1, y1, (double)acc[b][3]);
-                }
-            }
-    }
-#pragma unroll
-    for (int b = 0; b < B; b++)
-#pragma unroll
-        for (int k = 0; k < 4; k++) acc[b][k] = vround<T>(v, acc[b][k]);
-}
-
-// 2x2 blocks (i0, i0+1) × (j0[b], j0[b]+1), b < B, of the landmark block (i0, j0[b] even) as
-// they will be once the pending steps are flushed: per step (in order) a reset, or the rank-2m
-// downdate as the k-ordered FMA chain the MFMA executes, then the step's augmented rows rounded
-// to storage. The B blocks share one pass over the pending steps so that their loads overlap.
-template <typename T, int B>
-__device__ __forceinline__ void pll_blocks(const PllView<T>& v, int i0, const int (&j0)[B], double (&out)[B][4])
-{
-    using C = typename Stor<T>::C;
-    bool swap[B];
-    int a0[B], b0[B];
-    C acc[B][4];
-#pragma unroll
-    for (int b = 0; b < B; b++) {
-        swap[b] = (i0 >> 5) > (j0[b] >> 5);
-        a0[b] = swap[b] ? j0[b] : i0;   // stored orientation
-        b0[b] = swap[b] ? i0 : j0[b];
-        load_block<T>(v, a0[b], b0[b], acc[b]);
-    }
-    for (int q = 0; q < v.npend; q++) {
-        const Slot& sq = v.pend[q];
-        const int4 cw = v.ctl[q];
-        if (cw.x) {
-#pragma unroll
-            for (int b = 0; b < B; b++) acc[b][0] = acc[b][1] = acc[b][2] = acc[b][3] = (C)0;
-            continue;
-        }
-        const int ks = cw.y;
-        if (ks > 0 && B > 1) {
-            // several blocks: the owned rows' U and V loaded once per k-chunk, each column's
-            // one operand per block (a block stored in owned-first orientation runs U_own·V_col,
-            // a transposed one U_col·V_own): the same operands as the per-block form below
-            pll_shared_step<T, B>(v, sq, ks, i0, j0, swap, acc);
-        } else if (ks > 0) {
-            if constexpr (sizeof(C) == 4) {
-                // v_mfma_f32_32x32x2_f32 = ordered fmaf chain (k0 lanes 0-31, then k1)
-                const int kh = v.kmax / 2;
-                const float* ua[B];
-                const float* vb[B];
-#pragma unroll
-                for (int b = 0; b < B; b++) {
-                    ua[b] = u_rows_f32(v, sq) + ((size_t)(a0[b] >> 5) * 64 + (a0[b] & 31)) * kh;   // row a0; a0+1 at +kh
-                    vb[b] = reinterpret_cast<const float*>(sq.Vop) + v.e * v.opstride +
-                            ((size_t)(b0[b] >> 5) * 64 + (b0[b] & 31)) * kh;
-                }
-                for (int s0 = 0; s0 < ks; s0 += 4) {
-                    f32x4v ae0[B], ae1[B], ao0[B], ao1[B], be0[B], be1[B], bo0[B], bo1[B];
-#pragma unroll
-                    for (int b = 0; b < B; b++) {
-                        ae0[b] = *reinterpret_cast<const f32x4v*>(ua[b] + s0) * v.us;
-                        ae1[b] = *reinterpret_cast<const f32x4v*>(ua[b] + kh + s0) * v.us;
-                        ao0[b] = *reinterpret_cast<const f32x4v*>(ua[b] + 32 * kh + s0) * v.us;
-                        ao1[b] = *reinterpret_cast<const f32x4v*>(ua[b] + 33 * kh + s0) * v.us;
-                        be0[b] = *reinterpret_cast<const f32x4v*>(vb[b] + s0);
-                        be1[b] = *reinterpret_cast<const f32x4v*>(vb[b] + kh + s0);
-                        bo0[b] = *reinterpret_cast<const f32x4v*>(vb[b] + 32 * kh + s0);
-                        bo1[b] = *reinterpret_cast<const f32x4v*>(vb[b] + 33 * kh + s0);
-                    }
-#pragma unroll
-                    for (int s = 0; s < 4; s++) {
-                        if (s0 + s >= ks) break;
-#pragma unroll
-                        for (int b = 0; b < B; b++) {
-                            acc[b][0] = fmaf(ao0[b][s], bo0[b][s], fmaf(ae0[b][s], be0[b][s], acc[b][0]));
-                            acc[b][1] = fmaf(ao0[b][s], bo1[b][s], fmaf(ae0[b][s], be1[b][s], acc[b][1]));
-                            acc[b][2] = fmaf(ao1[b][s], bo0[b][s], fmaf(ae1[b][s], be0[b][s], acc[b][2]));
-                            acc[b][3] = fmaf(ao1[b][s], bo1[b][s], fmaf(ae1[b][s], be1[b][s], acc[b][3]));
-                        }
-                    }
-                }
-            } else {
-                // v_mfma_f64_16x16x4_f64 = ordered fma chain over k = 4s..4s+3
-                const int kq = v.kmax / 4;
-                const double* ua[B];
-                const double* vb[B];
-#pragma unroll
-                for (int b = 0; b < B; b++) {
-                    ua[b] = reinterpret_cast<const double*>(sq.Uop) + v.e * v.opstride +
-                            ((size_t)(a0[b] >> 5) * 64 + (a0[b] & 15)) * (2 * kq) + ((a0[b] >> 4) & 1) * kq;
-                    vb[b] = reinterpret_cast<const double*>(sq.Vop) + v.e * v.opstride +
-                            ((size_t)(b0[b] >> 5) * 64 + (b0[b] & 15)) * (2 * kq) + ((b0[b] >> 4) & 1) * kq;
-                }
-                for (int s = 0; s < ks; s++)
-#pragma unroll
-                    for (int kk = 0; kk < 4; kk++) {
-                        const size_t o = (size_t)16 * kk * 2 * kq + s;
-#pragma unroll
-                        for (int b = 0; b < B; b++) {
-                            const double x0 = ua[b][o], x1 = ua[b][o + 2 * kq];
-                            const double y0 = vb[b][o], y1 = vb[b][o + 2 * kq];
-                            acc[b][0] = fma(x0, y0, (double)acc[b][0]);
-                            acc[b][1] = fma(x0, y1, (double)acc[b][1]);
-                            acc[b][2] = fma(x1, y0, (double)acc[b][2]);
-                            acc[b][3] = fma(x1, y1, (double)acc[b][3]);
-                        }
-                    }
-            }
-#pragma unroll
-            for (int b = 0; b < B; b++)
-#pragma unroll
-                for (int k = 0; k < 4; k++) acc[b][k] = vround<T>(v, acc[b][k]);
-        }
-        if (cw.z > 0) {
-#pragma unroll
-            for (int b = 0; b < B; b++) patch_block<T>(v, sq, cw, i0, j0[b], swap[b], acc[b]);
-        }
-    }
-#pragma unroll
-    for (int b = 0; b < B; b++) {
-        if (swap[b]) {
-            out[b][0] = from_domain<T>(acc[b][0], v.ex); out[b][1] = from_domain<T>(acc[b][2], v.ex);
-            out[b][2] = from_domain<T>(acc[b][1], v.ex); out[b][3] = from_domain<T>(acc[b][3], v.ex);
-        } else {
-            out[b][0] = from_domain<T>(acc[b][0], v.ex); out[b][1] = from_domain<T>(acc[b][1], v.ex);
-            out[b][2] = from_domain<T>(acc[b][2], v.ex); out[b][3] = from_domain<T>(acc[b][3], v.ex);
-        }
-    }
-}
-
-template <typename T>
-__device__ __forceinline__ void pll_block(const PllView<T>& v, int i0, int j0, double out[4])
-{
-    const int js[1] = {j0};
-    double o[1][4];
-    pll_blocks<T, 1>(v, i0, js, o);
-    out[0] = o[0][0]; out[1] = o[0][1]; out[2] = o[0][2]; out[3] = o[0][3];
-}
+// ekf_kernels.hip — the association kernels of the EKF-SLAM update: the association arithmetic and
+// the exchange, scan_kernel, and the kernels of an instance partitioned over ranks (the step overview:
+// ekf_device.h). Not compiled on its own: unit_scan*.hip and unit_shard_pack.hip include it and define
+// the launchers that instantiate their share of it.
+#include "ekf_device.h"
 
 // The association arithmetic contracts a·b + c only within one source expression, so a
 // function inlined into different kernels or phases rounds identically everywhere (the
 // speculative and sequential association paths must agree bit for bit).
 #pragma clang fp contract(on)
+
+namespace ekf {
 
 // Uniform per-line package published by the matching thread (LDS).
 enum {
@@ -1598,8 +1093,6 @@ __device__ __forceinline__ void m64_pair_block(const PllView<T>& v, int wa, int 
 // negative or out-of-range row is a zero operand. Lane l holds ΔX[4·(l >> 4) + i][l & 15] of
 // M-block mb in acc[mb][i]. Not the fp32 chain of the flush (the split-bf16 flush is not one
 // either): held to the same parity bar.
-typedef __bf16 bf16x8r __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8r __attribute__((ext_vector_type(8)));
 // F16 (EKF_ARITH_F16X3): two fp16 planes (hi, lo of 2^σ·V), three products (lo, hi), (hi, lo),
 // (hi, hi) on v_mfma_f32_16x16x32_f16; acc then holds 2^(2σ)·ΔX (the caller scales it back)
 // BATCH pairs of pending steps per memory round trip: every operand load of the BATCH pairs is
@@ -4615,2589 +4108,5 @@ __global__ __launch_bounds__(SPR_THREADS) void shard_spec_kernel(ShardParams p)
         if (tid < 12) p.rob[tid] = sh_robl[first][tid];
     }
 }
-
-#pragma clang fp contract(fast)
-
-// ---------------------------------------------------------------------------------------
-// 2. covariance downdate of the landmark block on MFMA, one pass for a group of steps
-// ---------------------------------------------------------------------------------------
-// For every stored 32×32 tile and every step of the group, in order: the capacity reset
-// (Robot.cpp:893-904), or X ← X − U_t·V_tᵀ summed over the step's matches (rank 2m, the
-// reference's m dense passes of Robot.cpp:560-572) followed by the rows of the landmarks that
-// step appended (Robot.cpp:845-862). The tile stays in the MFMA accumulators for the whole
-// group: one HBM read and one write per tile per group.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-// value of landmark-block element (i, j) written by a step's augmentation
-__device__ __forceinline__ double patched_value(const double* prw0, const double* pdg, int M,
-                                                int s0, int i, int j)
-{
-    const int li = i >> 1, lj = j >> 1;
-    const int hi = li > lj ? li : lj;
-    const int qa = hi - s0;
-    if (li == lj) return pdg[qa * 4 + (i & 1) * 2 + (j & 1)];
-    const double* prw = prw0 + (size_t)qa * 2 * M;
-    return (li > lj) ? prw[(size_t)(i & 1) * M + j] : prw[(size_t)(j & 1) * M + i];
-}
-
-// fp32-layout tiles in fp32 or fp16 storage: lane's 4 consecutive elements of accumulator group qq
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-template <typename TS>
-__device__ __forceinline__ f32x4 tile_ld(const TS* tile, int lane, int qq)
-{
-    if constexpr (sizeof(TS) == 4) {
-        return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(tile) + lane + qq * 64);
-    } else {
-        const f16x4 h = __builtin_nontemporal_load(reinterpret_cast<const f16x4*>(tile) + lane + qq * 64);
-        return f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
-    }
-}
-
-template <typename TS>
-__device__ __forceinline__ void tile_st(TS* tile, int lane, int qq, const f32x16& a)
-{
-    if constexpr (sizeof(TS) == 4) {
-        const f32x4 v = {a[4 * qq + 0], a[4 * qq + 1], a[4 * qq + 2], a[4 * qq + 3]};
-        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(tile) + lane + qq * 64);
-    } else {
-        const f16x4 v = {(_Float16)a[4 * qq + 0], (_Float16)a[4 * qq + 1], (_Float16)a[4 * qq + 2],
-                         (_Float16)a[4 * qq + 3]};
-        __builtin_nontemporal_store(v, reinterpret_cast<f16x4*>(tile) + lane + qq * 64);
-    }
-}
-
-
-// fp16 storage: the value a step leaves in the block is its fp16 rounding (see Stor)
-template <typename TS>
-__device__ __forceinline__ void round_acc(f32x16& a)
-{
-    if constexpr (sizeof(TS) == 2) {
-#pragma unroll
-        for (int k = 0; k < 16; k++) a[k] = round_step<_Float16>(a[k]);
-    }
-}
-
-// f32 flush on super-tiles: a workgroup owns DD_SB × DD_SB tiles (wave w: tile row
-// sbi·DD_SB + w, tile columns sbj·DD_SB + 0..3), keeps their 4 accumulators in registers for
-// the whole group of steps and stages each step's operands for the DD_SB row blocks and DD_SB
-// column blocks through LDS in chunks of 8 MFMA k-steps (double-buffered, one barrier per
-// chunk, next chunk prefetched into registers while the current one runs). Operand traffic
-// per tile and k-step falls from 512 B to 128 B; the MFMA chain per element is unchanged
-// (k-ordered within a step, steps in order), so results are bit-identical to the per-tile form.
-namespace {
-constexpr int SBK = 8;   // MFMA k-steps per staged chunk (2 float4 per lane per block)
-
-struct SbStep {
-    int reset, ks, nadd, s0;
-};
-
-__device__ __forceinline__ SbStep sb_step(const DowndateParams& p, int q, int e)
-{
-    const int* r = p.steps[q].res + (size_t)e * RES_STRIDE;
-    SbStep s;
-    s.reset = r[RES_RESET];
-    s.ks = s.reset ? 0 : r[RES_KSTEPS];
-    s.nadd = r[RES_NADD];
-    s.s0 = r[RES_SAVED_IN];
-    return s;
-}
-}  // namespace
-
-template <typename TS>
-__global__ __launch_bounds__(DD_THREADS) void flush_f32_sb_kernel(DowndateParams p)
-{
-    const Dims d = p.d;
-    const int nsb = (d.nb + DD_SB - 1) / DD_SB;
-    const int64_t nst = (int64_t)nsb * (nsb + 1) / 2;
-    const int64_t total = (int64_t)p.E * nst;
-    // XCD-aware order: the hardware deals workgroup b to XCD b mod 8; give every XCD a
-    // contiguous range of (instance, super-tile) so that its L2 holds one instance's operands
-    const int64_t per = (total + 7) / 8;
-    const int64_t g = (int64_t)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (g >= total) return;
-    const int e = (int)(g / nst);
-    const int2 sb = p.stile_rc[g - (int64_t)e * nst];
-    const int lane = threadIdx.x & 63;
-    const int w = threadIdx.x >> 6;
-    const int bi = sb.x * DD_SB + w;
-    const int kh = d.kmax / 2;
-    const size_t opstride = (size_t)d.nb * 64 * kh;
-
-    // does any step change this super-tile? (uniform)
-    bool work = false;
-    for (int q = 0; q < p.nsteps; q++) {
-        const SbStep s = sb_step(p, q, e);
-        work |= s.reset || s.ks > 0 ||
-                (s.nadd > 0 && (sb.y + 1) * DD_SB * 16 > s.s0 && sb.y * DD_SB * 16 < s.s0 + s.nadd);
-    }
-    bool valid[DD_SB];
-    size_t toff[DD_SB];
-    int vmask = 0;
-#pragma unroll
-    for (int c = 0; c < DD_SB; c++) {
-        const int bj = sb.y * DD_SB + c;
-        valid[c] = bi < d.nb && bj < d.nb && bi <= bj;
-        vmask |= valid[c] << c;
-        toff[c] = valid[c] ? ((size_t)e * d.ntiles + tile_index(bi, bj, d.nb)) * TILE_ELEMS : 0;
-    }
-    const TS* Pin = reinterpret_cast<const TS*>(p.Pin);
-    TS* Pout = reinterpret_cast<TS*>(p.Pout);
-    if (!work) {
-        if (p.Pin != p.Pout) {
-#pragma unroll
-            for (int c = 0; c < DD_SB; c++)
-                if (valid[c]) {
-                    f32x16 t;
-#pragma unroll
-                    for (int qq = 0; qq < 4; qq++) {
-                        const f32x4 v = tile_ld(Pin + toff[c], lane, qq);
-                        t[4 * qq + 0] = v[0]; t[4 * qq + 1] = v[1]; t[4 * qq + 2] = v[2]; t[4 * qq + 3] = v[3];
-                    }
-#pragma unroll
-                    for (int qq = 0; qq < 4; qq++) tile_st(Pout + toff[c], lane, qq, t);
-                }
-        }
-        return;
-    }
-    f32x16 acc[DD_SB];
-#pragma unroll
-    for (int c = 0; c < DD_SB; c++) {
-        if (valid[c]) {
-#pragma unroll
-            for (int qq = 0; qq < 4; qq++) {
-                const f32x4 v = tile_ld(Pin + toff[c], lane, qq);
-                acc[c][4 * qq + 0] = v[0];
-                acc[c][4 * qq + 1] = v[1];
-                acc[c][4 * qq + 2] = v[2];
-                acc[c][4 * qq + 3] = v[3];
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 16; k++) acc[c][k] = 0.f;
-        }
-    }
-
-    // [buf][A/B][block][s4][lane] float4: 2 × 2 × 4 × 2 × 64 × 16 B = 32 KB
-    __shared__ f32x4 lds[2][2][DD_SB][2][64];
-    // staging: thread t moves float4 i = t + 256 j (j < 4): lane, s4, block, A/B
-    const float us = us_of<TS>(p, e);
-    auto fetch = [&](int q, int k0, f32x4 reg[4]) {
-        const float* U = u_rows_flush(p, p.steps[q], e, opstride);
-        const float* V = reinterpret_cast<const float*>(p.steps[q].Vop) + e * opstride;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int i = threadIdx.x + 256 * j;
-            const int ln = i & 63, s4 = (i >> 6) & 1, blk = (i >> 7) & 3, ab = i >> 9;
-            const int rb = (ab ? sb.y : sb.x) * DD_SB + blk;
-            if (rb < d.nb) {
-                const float* src = (ab ? V : U) + ((size_t)rb * 64 + ln) * kh + k0 + 4 * s4;
-                reg[j] = *reinterpret_cast<const f32x4*>(src) * (ab ? 1.0f : us);
-            }
-        }
-    };
-    auto stage = [&](int buf, const f32x4 reg[4]) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int i = threadIdx.x + 256 * j;
-            const int ln = i & 63, s4 = (i >> 6) & 1, blk = (i >> 7) & 3, ab = i >> 9;
-            lds[buf][ab][blk][s4][ln] = reg[j];
-        }
-    };
-    // reset or augmented rows of step q, after its downdate
-    auto post = [&](int q) {
-        const SbStep s = sb_step(p, q, e);
-        if (s.reset) {
-#pragma unroll
-            for (int c = 0; c < DD_SB; c++)
-#pragma unroll
-                for (int k = 0; k < 16; k++) acc[c][k] = 0.f;
-            return;
-        }
-        if (s.nadd <= 0) return;
-        const double* prw0 = p.steps[q].patch + (size_t)e * d.max_lines * 2 * d.M;
-        const double* pdg = p.steps[q].patch_diag + (size_t)e * d.max_lines * 4;
-        // one tile at a time through acc[0], rotating the four accumulators (rare path: keeps
-        // a single copy of the per-element code and its registers)
-#pragma nounroll
-        for (int c = 0; c < DD_SB; c++) {
-            const int bj = sb.y * DD_SB + c;
-            if (((vmask >> c) & 1) && bj * 16 + 15 >= s.s0 && bj * 16 < s.s0 + s.nadd) {
-                const int col = bj * 32 + (lane & 31);
-#pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    const int row = bi * 32 + (k & 3) + 8 * (k >> 2) + 4 * (lane >> 5);
-                    const int hi = max(row >> 1, col >> 1);
-                    if (hi >= s.s0 && hi < s.s0 + s.nadd)
-                        acc[0][k] = round_step<TS>(to_domain<TS>(patched_value(prw0, pdg, d.M, s.s0, row, col), storage_exp<TS>(p.pexp, e)));
-                }
-            }
-            const f32x16 t0 = acc[0];
-            acc[0] = acc[1];
-            acc[1] = acc[2];
-            acc[2] = acc[3];
-            acc[3] = t0;
-        }
-    };
-    // first chunk at or after step q (k0 = 0): steps without a downdate are passed through post
-    auto first_mfma = [&](int q) {
-        while (q < p.nsteps && sb_step(p, q, e).ks == 0) q++;
-        return q;
-    };
-
-    int q = first_mfma(0);
-    for (int t = 0; t < q; t++) post(t);
-    int k0 = 0, buf = 0;
-    f32x4 reg[4];
-    if (q < p.nsteps) fetch(q, 0, reg);
-    while (q < p.nsteps) {
-        const int ks = sb_step(p, q, e).ks;
-        const int kc = min(SBK, ks - k0);
-        stage(buf, reg);
-        __syncthreads();
-        // next chunk
-        int qn = q, kn = k0 + SBK;
-        if (kn >= ks) {
-            qn = first_mfma(q + 1);
-            kn = 0;
-        }
-        if (qn < p.nsteps) fetch(qn, kn, reg);
-        const f32x4 a0 = lds[buf][0][w][0][lane];
-        const f32x4 a1 = lds[buf][0][w][1][lane];
-        f32x4 b0[DD_SB], b1[DD_SB];
-#pragma unroll
-        for (int c = 0; c < DD_SB; c++) {
-            b0[c] = lds[buf][1][c][0][lane];
-            b1[c] = lds[buf][1][c][1][lane];
-        }
-        {
-#pragma unroll
-            for (int s = 0; s < SBK; s++)
-                if (s < kc) {
-#pragma unroll
-                    for (int c = 0; c < DD_SB; c++)
-                        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(s < 4 ? a0[s & 3] : a1[s & 3],
-                                                                      s < 4 ? b0[c][s & 3] : b1[c][s & 3],
-                                                                      acc[c], 0, 0, 0);
-                }
-        }
-        if (qn != q) {
-#pragma unroll
-            for (int c = 0; c < DD_SB; c++) round_acc<TS>(acc[c]);
-            for (int t = q; t < qn && t < p.nsteps; t++) post(t);
-        }
-        q = qn;
-        k0 = kn;
-        buf ^= 1;
-    }
-#pragma unroll
-    for (int c = 0; c < DD_SB; c++)
-        if (valid[c]) {
-#pragma unroll
-            for (int qq = 0; qq < 4; qq++) tile_st(Pout + toff[c], lane, qq, acc[c]);
-        }
-}
-
-// Groups of at most PST_MAXC steps with kmax <= 16 (one operand chunk per step) run the
-// persistent form below; otherwise flush_f32_sb_kernel runs.
-constexpr int PST_MAXC = 4;
-
-// scalar (constant address space) load of a wave-uniform word that no kernel of this launch
-// writes: keeps the control words on lgkmcnt, out of the vmcnt queue the prefetch occupies
-template <typename T>
-__device__ __forceinline__ T sload(const T* ptr)
-{
-    return *(const __attribute__((address_space(4))) T*)(ptr);
-}
-
-// f32/f16 flush, persistent 2-workgroups-per-CU form: super-tiles of 4 × 2 tiles (wave w: tile
-// row sbi·4 + w, tile columns sbj·2 + 0..1), two accumulators per wave, single-buffered LDS
-// operands (48 KB: 4 A blocks + 2 B blocks per chunk), two barriers per super-tile. Two
-// independent workgroups per CU (≤ 256 registers per wave) let one workgroup's MFMA chains run
-// while the other stages, waits or streams. Per super-tile the control is four scalar words
-// (instance, super-tile, packed step flags); when every step of the group is a full 8-k-step
-// downdate with nothing else to apply (the steady state) the MFMA block runs without predicates.
-constexpr int P2_C = 2;   // tile columns per super-tile
-
-struct P2Info {
-    int e, sbi, sbj;
-    int flags;   // per step q, byte q: bits 0-3 ks, bit 4 reset, bit 5 augmented rows present
-};
-
-template <typename TS>
-__global__ __launch_bounds__(DD_THREADS, 2) void flush_f32_persist2_kernel(DowndateParams p)
-{
-    const Dims d = p.d;
-    const int nst = p.nstiles2;
-    const int total = p.E * nst;
-    const int per = (total + 7) / 8;
-    const int xcd = blockIdx.x & 7;
-    const int wpx = gridDim.x >> 3;
-    const int g_end = min(total, (xcd + 1) * per);
-    int g = xcd * per + (blockIdx.x >> 3);
-    if (g >= g_end) return;
-
-    const int lane = threadIdx.x & 63;
-    const int w = threadIdx.x >> 6;
-    const int kh = d.kmax / 2;
-    const size_t opstride = (size_t)d.nb * 64 * kh;
-    const TS* Pin = reinterpret_cast<const TS*>(p.Pin);
-    TS* Pout = reinterpret_cast<TS*>(p.Pout);
-    const int nsteps = p.nsteps;
-    // this thread's staging slots j < 3 of a chunk: float4 i = tid + 256 j of
-    // [A: 4 blocks × 2 × 64 | B: 2 blocks × 2 × 64]; offsets inside a block row are invariant
-    const int ln = threadIdx.x & 63, s4 = (threadIdx.x >> 6) & 1, bl = threadIdx.x >> 7;
-    const int in_blk = ln * kh + 4 * s4;
-
-    auto load_flags = [&](P2Info& t) {
-        int f = 0;
-#pragma unroll
-        for (int q = 0; q < PST_MAXC; q++) {
-            if (q < nsteps) {
-                const int* r = p.steps[q].res + (size_t)t.e * RES_STRIDE;
-                const int reset = sload(r + RES_RESET);
-                const int ks = reset ? 0 : sload(r + RES_KSTEPS);
-                const int nadd = sload(r + RES_NADD);
-                f |= ((ks & 15) | (reset ? 16 : 0) | (nadd > 0 ? 32 : 0)) << (8 * q);
-            }
-        }
-        t.flags = f;
-    };
-    auto locate = [&](int li, P2Info& t) {
-        const int* rc = reinterpret_cast<const int*>(p.stile2_rc + li);
-        t.sbi = sload(rc);
-        t.sbj = sload(rc + 1);
-    };
-    auto tile_off = [&](const P2Info& t, int c, bool& valid) {
-        const int bi = t.sbi * DD_SB + w, bj = t.sbj * P2_C + c;
-        valid = bi < d.nb && bj < d.nb && bi <= bj;
-        return valid ? ((size_t)t.e * d.ntiles + tile_index(bi, bj, d.nb)) * TILE_ELEMS : (size_t)0;
-    };
-    auto fetch = [&](const P2Info& t, f32x4 opreg[PST_MAXC][3], f32x4 pref[P2_C][4]) {
-        const int rA0 = min(t.sbi * DD_SB + bl, d.nb - 1), rA1 = min(t.sbi * DD_SB + 2 + bl, d.nb - 1);
-        const int rB = min(t.sbj * P2_C + bl, d.nb - 1);   // rows past the block: unused
-#pragma unroll
-        for (int c = 0; c < PST_MAXC; c++) {
-            const int qc = ((t.flags >> (8 * c)) & 15) ? c : 0;   // absent steps re-read step 0
-            const float* U = u_rows_flush(p, p.steps[qc], t.e, opstride);
-            const float* V = reinterpret_cast<const float*>(p.steps[qc].Vop) + t.e * opstride;
-            const float us = us_of<TS>(p, t.e);
-            opreg[c][0] = *reinterpret_cast<const f32x4*>(U + (size_t)rA0 * 64 * kh + in_blk) * us;
-            opreg[c][1] = *reinterpret_cast<const f32x4*>(U + (size_t)rA1 * 64 * kh + in_blk) * us;
-            opreg[c][2] = *reinterpret_cast<const f32x4*>(V + (size_t)rB * 64 * kh + in_blk);
-        }
-#pragma unroll
-        for (int c = 0; c < P2_C; c++) {
-            bool v;
-            const TS* tl = Pin + tile_off(t, c, v);
-#pragma unroll
-            for (int qq = 0; qq < 4; qq++) pref[c][qq] = tile_ld(tl, lane, qq);
-        }
-    };
-    __shared__ f32x4 ldsA[PST_MAXC][DD_SB][2][64];   // 32 KB
-    __shared__ f32x4 ldsB[PST_MAXC][P2_C][2][64];    // 16 KB
-    P2Info cur;
-    cur.e = __builtin_amdgcn_readfirstlane(g / nst);
-    int li = __builtin_amdgcn_readfirstlane(g - cur.e * nst);
-    locate(li, cur);
-    load_flags(cur);
-    f32x4 opreg[PST_MAXC][3];
-    f32x4 pref[P2_C][4];
-    fetch(cur, opreg, pref);
-    f32x16 acc[P2_C];
-    // steady state: every step of the group a full chunk, no reset, no augmented rows
-    int steady = 0;
-#pragma unroll
-    for (int q = 0; q < PST_MAXC; q++) steady |= (q < nsteps ? SBK : 0) << (8 * q);
-
-    while (true) {
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS free
-#pragma unroll
-        for (int c = 0; c < PST_MAXC; c++) {
-            if ((cur.flags >> (8 * c)) & 15) {
-                ldsA[c][bl][s4][ln] = opreg[c][0];
-                ldsA[c][2 + bl][s4][ln] = opreg[c][1];
-                ldsB[c][bl][s4][ln] = opreg[c][2];
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS written
-#pragma unroll
-        for (int c = 0; c < P2_C; c++)
-#pragma unroll
-            for (int qq = 0; qq < 4; qq++) {
-                acc[c][4 * qq + 0] = pref[c][qq][0];
-                acc[c][4 * qq + 1] = pref[c][qq][1];
-                acc[c][4 * qq + 2] = pref[c][qq][2];
-                acc[c][4 * qq + 3] = pref[c][qq][3];
-            }
-        // next super-tile in flight (the last iteration re-reads its own)
-        const int gn = g + wpx;
-        const bool more = gn < g_end;
-        P2Info nxt;
-        nxt.e = cur.e;
-        int lin = li;
-        if (more) {
-            lin += wpx;
-            while (lin >= nst) {
-                lin -= nst;
-                nxt.e++;
-            }
-        }
-        locate(lin, nxt);
-        load_flags(nxt);
-        fetch(nxt, opreg, pref);
-
-        const int e = cur.e;
-        const int bi = cur.sbi * DD_SB + w;
-        if (cur.flags == steady) {
-            __builtin_amdgcn_s_setprio(1);   // this MFMA cluster ahead of the partner's staging
-#pragma unroll
-            for (int q = 0; q < PST_MAXC; q++) {
-                if (q < nsteps) {
-                    const f32x4 a0 = ldsA[q][w][0][lane];
-                    const f32x4 a1 = ldsA[q][w][1][lane];
-                    const f32x4 b00 = ldsB[q][0][0][lane], b01 = ldsB[q][0][1][lane];
-                    const f32x4 b10 = ldsB[q][1][0][lane], b11 = ldsB[q][1][1][lane];
-#pragma unroll
-                    for (int s = 0; s < 4; s++) {
-                        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[s], b00[s], acc[0], 0, 0, 0);
-                        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[s], b10[s], acc[1], 0, 0, 0);
-                    }
-#pragma unroll
-                    for (int s = 0; s < 4; s++) {
-                        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[s], b01[s], acc[0], 0, 0, 0);
-                        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[s], b11[s], acc[1], 0, 0, 0);
-                    }
-                    round_acc<TS>(acc[0]);
-                    round_acc<TS>(acc[1]);
-                }
-            }
-            __builtin_amdgcn_s_setprio(0);
-        } else {
-            int vmask = 0;
-#pragma unroll
-            for (int c = 0; c < P2_C; c++) {
-                bool v;
-                (void)tile_off(cur, c, v);
-                vmask |= (int)v << c;
-            }
-            auto post = [&](int q) {
-                const int fq = (cur.flags >> (8 * q)) & 255;
-                if (fq & 16) {
-#pragma unroll
-                    for (int c = 0; c < P2_C; c++)
-#pragma unroll
-                        for (int k = 0; k < 16; k++) acc[c][k] = 0.f;
-                    return;
-                }
-                if (!(fq & 32)) return;
-                const int* r = p.steps[q].res + (size_t)e * RES_STRIDE;
-                const int nadd = sload(r + RES_NADD), s0 = sload(r + RES_SAVED_IN);
-                if ((cur.sbj + 1) * P2_C * 16 <= s0 || cur.sbj * P2_C * 16 >= s0 + nadd) return;
-                const double* prw0 = p.steps[q].patch + (size_t)e * d.max_lines * 2 * d.M;
-                const double* pdg = p.steps[q].patch_diag + (size_t)e * d.max_lines * 4;
-                const int ex = storage_exp<TS>(p.pexp, e);
-#pragma nounroll
-                for (int c = 0; c < P2_C; c++) {
-                    const int bj = cur.sbj * P2_C + c;
-                    if (((vmask >> c) & 1) && bj * 16 + 15 >= s0 && bj * 16 < s0 + nadd) {
-                        const int col = bj * 32 + (lane & 31);
-#pragma unroll
-                        for (int k = 0; k < 16; k++) {
-                            const int row = bi * 32 + (k & 3) + 8 * (k >> 2) + 4 * (lane >> 5);
-                            const int hi = max(row >> 1, col >> 1);
-                            if (hi >= s0 && hi < s0 + nadd)
-                                acc[0][k] = round_step<TS>(to_domain<TS>(patched_value(prw0, pdg, d.M, s0, row, col), ex));
-                        }
-                    }
-                    const f32x16 t0 = acc[0];
-                    acc[0] = acc[1];
-                    acc[1] = t0;
-                }
-            };
-#pragma unroll
-            for (int q = 0; q < PST_MAXC; q++) {
-                if (q >= nsteps) break;
-                const int kc = (cur.flags >> (8 * q)) & 15;
-                if (kc > 0) {
-                    const f32x4 a0 = ldsA[q][w][0][lane];
-                    const f32x4 a1 = ldsA[q][w][1][lane];
-                    f32x4 b0[P2_C], b1[P2_C];
-#pragma unroll
-                    for (int cc = 0; cc < P2_C; cc++) {
-                        b0[cc] = ldsB[q][cc][0][lane];
-                        b1[cc] = ldsB[q][cc][1][lane];
-                    }
-#pragma unroll
-                    for (int s = 0; s < SBK; s++)
-                        if (s < kc) {
-#pragma unroll
-                            for (int cc = 0; cc < P2_C; cc++)
-                                acc[cc] = __builtin_amdgcn_mfma_f32_32x32x2f32(s < 4 ? a0[s & 3] : a1[s & 3],
-                                                                               s < 4 ? b0[cc][s & 3] : b1[cc][s & 3],
-                                                                               acc[cc], 0, 0, 0);
-                        }
-#pragma unroll
-                    for (int cc = 0; cc < P2_C; cc++) round_acc<TS>(acc[cc]);
-                }
-                post(q);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < P2_C; c++) {
-            bool v;
-            const size_t off = tile_off(cur, c, v);
-            if (v) {
-#pragma unroll
-                for (int qq = 0; qq < 4; qq++) tile_st(Pout + off, lane, qq, acc[c]);
-            }
-        }
-        if (!more) break;
-        g = gn;
-        li = lin;
-        cur = nxt;
-    }
-}
-
-// One WT_R × WT_C wave-tile (instance e, table entry w) through a group of NS steps in order, operands
-// loaded in place: per step its reset, or the rank-2m downdate (v_mfma_f32_32x32x2_f32, the exact
-// k-ordered chain, fp16 rounding per step; once per group, at the store, under p.bf) and then its augmented rows (one tile at a time through
-// acc[0], rotating the accumulators). Tiles outside the triangle are stored to the sink tile. The
-// general path of the wave flushes (groups with a reset or new rows in some instance of the wave).
-template <typename TS, int NS>
-__device__ __forceinline__ void wt_general(const DowndateParams& p, int e, const WtEntry& w, int lane)
-{
-    const Dims d = p.d;
-    const int kh = d.kmax / 2;
-    const size_t opstride = (size_t)d.nb * 64 * kh;
-    const size_t inst_elems = (size_t)d.ntiles * TILE_ELEMS;
-    const TS* Pin = reinterpret_cast<const TS*>(p.Pin);
-    TS* Pout = reinterpret_cast<TS*>(p.Pout);
-    TS* sink = reinterpret_cast<TS*>(p.sink);
-    const int lofs = lane * kh;
-    auto op_row = [&](int side, int k) { return (w.rows[side] >> (16 * k)) & 0xffff; };
-    f32x16 acc[WT_N];
-#pragma unroll
-    for (int i = 0; i < WT_N; i++) {
-        const TS* tl = Pin + (size_t)e * inst_elems + (size_t)w.tile[i] * TILE_ELEMS;
-#pragma unroll
-        for (int qq = 0; qq < 4; qq++) {
-            const f32x4 v = tile_ld(tl, lane, qq);
-#pragma unroll
-            for (int j = 0; j < 4; j++) acc[i][4 * qq + j] = v[j];
-        }
-    }
-    const int wr = w.rc & 0xffff, wc = w.rc >> 16;
-    for (int q = 0; q < NS; q++) {
-        const int* r = p.steps[q].res + (size_t)e * RES_STRIDE;
-        const int reset = sload(r + RES_RESET);
-        const int kc = reset ? 0 : sload(r + RES_KSTEPS);
-        if (kc > 0) {
-            const float* U = u_rows_flush(p, p.steps[q], e, opstride) + lofs;
-            const float* V = reinterpret_cast<const float*>(p.steps[q].Vop) + e * opstride + lofs;
-            const float us = us_of<TS>(p, e);
-            f32x4 a[WT_R][2], b[WT_C][2];
-#pragma unroll
-            for (int rr = 0; rr < WT_R; rr++) {
-                const float* src = U + (size_t)op_row(0, rr) * 64 * kh;
-                a[rr][0] = *reinterpret_cast<const f32x4*>(src) * us;
-                a[rr][1] = *reinterpret_cast<const f32x4*>(src + 4) * us;
-            }
-#pragma unroll
-            for (int c = 0; c < WT_C; c++) {
-                const float* src = V + (size_t)op_row(1, c) * 64 * kh;
-                b[c][0] = *reinterpret_cast<const f32x4*>(src);
-                b[c][1] = *reinterpret_cast<const f32x4*>(src + 4);
-            }
-#pragma unroll
-            for (int s = 0; s < SBK; s++)
-                if (s < kc) {
-#pragma unroll
-                    for (int rr = 0; rr < WT_R; rr++)
-#pragma unroll
-                        for (int c = 0; c < WT_C; c++)
-                            acc[rr * WT_C + c] = __builtin_amdgcn_mfma_f32_32x32x2f32(
-                                a[rr][s >> 2][s & 3], b[c][s >> 2][s & 3], acc[rr * WT_C + c], 0, 0, 0);
-                }
-            if (!p.bf) {   // split-bf16 flushes round fp16 storage once per group (at the store)
-#pragma unroll
-                for (int i = 0; i < WT_N; i++) round_acc<TS>(acc[i]);
-            }
-        }
-        if (reset) {
-#pragma unroll
-            for (int i = 0; i < WT_N; i++)
-#pragma unroll
-                for (int k = 0; k < 16; k++) acc[i][k] = 0.f;
-            continue;
-        }
-        const int nadd = sload(r + RES_NADD), s0 = sload(r + RES_SAVED_IN);
-        if (nadd <= 0 || (wc + 1) * WT_C * 16 <= s0 || wc * WT_C * 16 >= s0 + nadd) continue;
-        const double* prw0 = p.steps[q].patch + (size_t)e * d.max_lines * 2 * d.M;
-        const double* pdg = p.steps[q].patch_diag + (size_t)e * d.max_lines * 4;
-        const int ex = storage_exp<TS>(p.pexp, e);
-#pragma nounroll
-        for (int i = 0; i < WT_N; i++) {
-            const int bi = wr * WT_R + i / WT_C, bj = wc * WT_C + i % WT_C;
-            if (((w.valid >> i) & 1) && bj * 16 + 15 >= s0 && bj * 16 < s0 + nadd) {
-                const int col = bj * 32 + (lane & 31);
-#pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    const int row = bi * 32 + (k & 3) + 8 * (k >> 2) + 4 * (lane >> 5);
-                    const int hi = max(row >> 1, col >> 1);
-                    if (hi >= s0 && hi < s0 + nadd) {
-                        const float v = to_domain<TS>(patched_value(prw0, pdg, d.M, s0, row, col), ex);
-                        acc[0][k] = p.bf ? v : round_step<TS>(v);
-                    }
-                }
-            }
-            const f32x16 t0 = acc[0];
-#pragma unroll
-            for (int j = 0; j < WT_N - 1; j++) acc[j] = acc[j + 1];
-            acc[WT_N - 1] = t0;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < WT_N; i++) {
-        TS* tl = ((w.valid >> i) & 1) ? Pout + (size_t)e * inst_elems + (size_t)w.tile[i] * TILE_ELEMS : sink;
-#pragma unroll
-        for (int qq = 0; qq < 4; qq++) tile_st(tl, lane, qq, acc[i]);
-    }
-}
-
-// f32/f16 flush, barrier-free per-wave form for groups of an even number of steps NS (2..8,
-// kmax <= 16). One wave per SIMD, each working alone (no LDS, no barriers) through a sequence of
-// wave-tiles of WT_R × WT_C tiles (four 32×32 accumulators). Software pipeline, one wave-tile
-// deep: while wave-tile k runs its NS·32 MFMAs, the tiles of wave-tile k+1 (issued first) and its
-// operand rows (step q's issued right after step q's MFMAs free their registers) stream into
-// registers, so every wait of a wave-tile covers only loads issued during the one before it. The
-// host table wt (WtEntry) gives each wave-tile's tile indices, operand row blocks and validity;
-// the entry of wave-tile k+2 is read (scalar loads) during wave-tile k. The wave-tiles of an
-// instance are walked in panels and each XCD takes a contiguous range of (instance, wave-tile),
-// so the wave-tiles an XCD has in flight share their operand rows in its L2. This pipelined loop
-// serves the groups in which no step of the wave's instances resets the map or adds landmarks
-// (partial downdates are predicated); otherwise the wave runs a plain per-wave-tile loop. Per
-// element the chain is the one every other form runs (k-ordered MFMA steps, fp16 rounding per
-// step, then the step's rows or the reset): bit-identical results.
-//
-// BF (EKF_ARITH_BF16X6, fp32 storage, symmetric operands): the plain groups run each step as six
-// v_mfma_f32_32x32x16_bf16 per accumulator on V's exact three-part bf16 split (the scan's
-// planes, Slot::Bop). With U = −V the accumulators hold −X (negated on load and store, exact), so
-// both operands are V planes: of the wave-tile's row blocks (A) and column blocks (B). Operands
-// stream through a ring of RD step-sets, RD − 1 steps ahead, across wave-tile boundaries.
-// split-plane flushes: one wave per SIMD (two at <= 256 registers and a ring of 2 measured equal;
-// scripts/xp/f16_wave_switches.patch restores that and the other A/B switches of this form)
-constexpr int F16_RDMAX = 8;   // split-fp16 flush: the deepest operand ring (step-sets)
-// the largest divisor of ns not above rmax (at least 2)
-constexpr int ring_depth(int ns, int rmax)
-{
-    int r = 2;
-    for (int k = 2; k <= rmax; k++)
-        if (ns % k == 0) r = k;
-    return r;
-}
-template <typename TS, int NS, bool BF = false, bool F16 = false>
-__global__ __launch_bounds__(DD_THREADS, 1) void flush_f32_wave_kernel(DowndateParams p)
-{
-    static_assert(NS >= 2 && NS % 2 == 0 && NS <= PMAX, "even step count");
-    static_assert(BF || NS <= 8, "fp32 wave flush: at most 8 steps (operands of every step in registers)");
-    constexpr bool HALF = sizeof(TS) == 2;
-    constexpr bool AM = HALF;   // fp16 storage: pair-major step order (below)
-    const Dims d = p.d;
-    const int nwt = p.nwt;
-    const int total = p.E * nwt;
-    const int per = (total + 7) / 8;
-    const int xcd = blockIdx.x & 7;
-    const int K = (int)(gridDim.x >> 3) * (DD_THREADS / 64);     // waves per XCD
-    const int g_end = min(total, (xcd + 1) * per);
-    const int g0 = __builtin_amdgcn_readfirstlane(
-        xcd * per + (int)(blockIdx.x >> 3) * (DD_THREADS / 64) + (int)(threadIdx.x >> 6));
-    if (g0 >= g_end) return;
-
-    const int lane = threadIdx.x & 63;
-    const int kh = d.kmax / 2;   // 8
-    const size_t opstride = (size_t)d.nb * 64 * kh;
-    const size_t inst_elems = (size_t)d.ntiles * TILE_ELEMS;
-    const TS* Pin = reinterpret_cast<const TS*>(p.Pin);
-    TS* Pout = reinterpret_cast<TS*>(p.Pout);
-    TS* sink = reinterpret_cast<TS*>(p.sink);
-    const int lofs = lane * kh;
-
-    // the pipelined loop needs every step of every instance this wave visits to be a plain
-    // downdate (no reset, no new rows); the split-plane form also takes steps that add rows (it
-    // writes them into the wave-tiles they touch, between the steps' MFMAs)
-    bool fast = true, fast_rows = true;
-    {
-        const int e_lo = g0 / nwt, e_hi = (g_end - 1) / nwt;
-        for (int e = e_lo; e <= e_hi; e++)
-#pragma unroll
-            for (int q = 0; q < NS; q++) {
-                const int* r = p.steps[q].res + (size_t)e * RES_STRIDE;
-                const bool rb = sload(r + RES_ROLLBACK), rs = sload(r + RES_RESET);
-                fast_rows = fast_rows && !rb;
-                fast = fast && !rb && !rs && sload(r + RES_NADD) == 0;
-            }
-    }
-
-    // a wave-tile: instance, table entry (scalar registers)
-    struct Item {
-        int e, li, g;   // instance, table entry, flat index (g0 + k·K)
-        WtEntry w;
-    };
-    typedef int i32x8 __attribute__((ext_vector_type(8)));
-    static_assert(sizeof(WtEntry) == sizeof(i32x8), "one scalar dwordx8 per entry");
-    auto load_entry = [&](int li, WtEntry& w) __attribute__((always_inline)) {
-        const i32x8 v = sload(reinterpret_cast<const i32x8*>(p.wt + li));
-#pragma unroll
-        for (int i = 0; i < WT_N; i++) w.tile[i] = v[i];
-        w.valid = v[WT_N];
-        w.rows[0] = v[WT_N + 1];
-        w.rows[1] = v[WT_N + 2];
-        w.rc = v[WT_N + 3];
-    };
-    // the wave's k-th wave-tile follows from the (k−1)-th by adding K to the flat index
-    auto first_item = [&](Item& t) __attribute__((always_inline)) {
-        t.e = g0 / nwt;
-        const int li = g0 - t.e * nwt;
-        load_entry(li, t.w);
-        t.li = li;
-        t.g = g0;
-    };
-    auto next_item = [&](const Item& c, Item& t) __attribute__((always_inline)) {
-        int li = c.li + K, e = c.e;
-        while (li >= nwt) {
-            li -= nwt;
-            e++;
-        }
-        t.e = e;
-        load_entry(e < p.E ? li : 0, t.w);
-        t.li = li;
-        t.g = c.g + K;
-    };
-    auto tile_ptr = [&](const Item& t, int i) __attribute__((always_inline)) {
-        return (size_t)t.e * inst_elems + (size_t)t.w.tile[i] * TILE_ELEMS;
-    };
-    // every slot is stored, the invalid ones (outside the packed triangle) to the sink tile: no
-    // branch around a store (a conditional store splits the wait-count tracking, and the join
-    // then waits for every outstanding load, the next wave-tile's prefetch included)
-    auto store_tiles = [&](const Item& t, const f32x16 (&acc)[WT_N], bool skip = false) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < WT_N; i++) {
-            TS* tl = ((t.w.valid >> i) & 1) && !skip ? Pout + tile_ptr(t, i) : sink;
-#pragma unroll
-            for (int qq = 0; qq < 4; qq++) tile_st(tl, lane, qq, acc[i]);
-        }
-    };
-    auto op_row = [&](const Item& t, int side, int k) __attribute__((always_inline)) {
-        return (t.w.rows[side] >> (16 * k)) & 0xffff;
-    };
-    // step q's operand rows (side 0: U, 1: V) from the contiguous slot buffers: scalar arithmetic
-    // on a few kernel arguments, not 2·NS pointers (which the compiler reloaded from the kernel
-    // arguments inside the loop, each load waited on before the next MFMA could issue)
-    auto op_base = [&](int q, int side) __attribute__((always_inline)) {
-        int sl = p.slot0 + q;
-        if (sl >= p.nslots) sl -= p.nslots;
-        return reinterpret_cast<const float*>(reinterpret_cast<const char*>(side || p.usym ? p.vbase : p.ubase) +
-                                              (size_t)sl * (size_t)p.slot_bytes);
-    };
-
-    if constexpr (BF) {
-        if (fast_rows) {
-            // planes: BF16X6 hi, mid, lo bf16 (six products); F16X3 hi, lo fp16 of 2^σ·V (three)
-            constexpr int NPL = F16 ? 2 : 3;
-            typedef typename std::conditional<F16, f16x8r, bf16x8r>::type bf16x8;
-            // operand ring depth (divides NS: a ring slot keeps its step index across wave-tiles).
-            // F16: the deepest ring of at most F16_RDMAX step-sets, and the next wave-tile's tiles
-            // issued RD − 1 steps before its start (late, below)
-            constexpr int RD = F16 ? ring_depth(NS, F16_RDMAX) : (NS % 4 == 0 ? 4 : (NS % 3 == 0 ? 3 : 2));
-            constexpr bool LATE = F16 && RD >= 3;
-            // vmcnt retires in issue order, so every operand wait after the tile loads also waits for
-            // them: issued at step TQ, the first such wait comes RD − 1 steps later, and so does
-            // the next wave-tile's first use of them
-            constexpr int TQ = NS - RD + 1;
-            const size_t pstride = (size_t)d.nb * NPL * 64;   // 16-byte operands per instance
-            // step q's planes: slot (slot0 + q) mod nslots
-            auto pl_base = [&](int q) __attribute__((always_inline)) {
-                int sl = p.slot0 + q;
-                if (sl >= p.nslots) sl -= p.nslots;
-                return reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(p.bbase) +
-                                                       (size_t)sl * (size_t)p.bslot_bytes);
-            };
-            // raw tile words in flight (fp16 storage: converted when the wave-tile starts)
-            using Raw = typename std::conditional<HALF, f16x4, f32x4>::type;
-            Raw pref[WT_N][4];
-            f32x16 acc[WT_N];
-            bf16x8 R[RD][WT_R + WT_C][NPL];
-            // step q of wave-tile t into ring set r: A row blocks, then B row blocks, three planes
-            auto load_ops = [&](int r, const Item& t, int q) __attribute__((always_inline)) {
-                const bf16x8* b = pl_base(q) + t.e * pstride + lane;
-#pragma unroll
-                for (int i = 0; i < WT_R + WT_C; i++) {
-                    const bf16x8* rb = b + (size_t)(i < WT_R ? op_row(t, 0, i) : op_row(t, 1, i - WT_R)) * NPL * 64;
-#pragma unroll
-                    for (int pl = 0; pl < NPL; pl++) R[r][i][pl] = rb[pl * 64];
-                }
-            };
-            auto load_tiles = [&](const Item& t) __attribute__((always_inline)) {
-#pragma unroll
-                for (int i = 0; i < WT_N; i++) {
-                    const Raw* tl = reinterpret_cast<const Raw*>(Pin + tile_ptr(t, i));
-#pragma unroll
-                    for (int qq = 0; qq < 4; qq++) pref[i][qq] = __builtin_nontemporal_load(tl + lane + qq * 64);
-                }
-            };
-            // the accumulators hold −P: fp32 storage −X; fp16 storage −2^−x·X (X = fp16(2^x·P), the
-            // instance's exponent; power-of-two scalings, exact), so that both operands are the
-            // unscaled V planes; the store scales back and rounds to fp16 once per group. F16X3: the
-            // planes of step q carry 2^σ_q·V, so during step q the accumulators hold −2^(2σ_q)·P (σ
-            // changes only at a step that adds rows: the accumulators are rescaled after it)
-            // per instance of the wave-tiles (uniform, few registers): the landmarks the group's steps
-            // add [u_lo, u_hi), σ of the first and last step, the steps after which σ changes
-            auto rec_of = [&](int e, int q, int w) __attribute__((always_inline)) {
-                return sload(p.steps[q].res + (size_t)e * RES_STRIDE + w);
-            };
-            // A step that resets the map (Robot.cpp:893-904) zeroes the block: only the landmarks
-            // added after the instance's last reset of the group are nonzero at its end, so the
-            // union is taken over those steps and every other wave-tile of the instance is stored
-            // as zero (rz); σ changes before that reset do not matter.
-            int st_e = -1, u_lo = 0, u_hi = 0, sg0 = 0, sgl = 0, zl = 0;
-            unsigned smask = 0;
-            bool rz = false;
-            auto load_steps = [&](int e) __attribute__((always_inline)) {
-                u_lo = 0x7fffffff;
-                u_hi = 0;
-                smask = 0;
-                rz = false;
-                zl = 0;   // landmarks past every step's RES_ZMAX: zero V rows, no new rows
-                int prev = 0;
-#pragma unroll
-                for (int q = 0; q < NS; q++) {
-                    zl = max(zl, rec_of(e, q, RES_ZMAX));
-                    if (rec_of(e, q, RES_RESET)) {   // (its own new rows are wiped with the map)
-                        u_lo = 0x7fffffff;
-                        u_hi = 0;
-                        smask = 0;
-                        rz = true;
-                        continue;
-                    }
-                    const int na = rec_of(e, q, RES_NADD), s0 = rec_of(e, q, RES_SAVED_IN);
-                    if (na > 0) {
-                        u_lo = min(u_lo, s0);
-                        u_hi = max(u_hi, s0 + na);
-                    }
-                    const int sg = F16 ? rec_of(e, q, RES_PSIG) : 0;
-                    if (q == 0) sg0 = sg;
-                    else if (sg != prev) smask |= 1u << (q - 1);
-                    if (sg == PLANE_SIGMA_EXACT) smask |= 1u << NS;   // (the whole group exact)
-                    prev = sg;
-                }
-                sgl = prev;
-                st_e = e;
-            };
-            auto in_exp = [&](const Item& t) __attribute__((always_inline)) {
-                int ex = 2 * sg0;
-                if constexpr (HALF) ex -= sload(p.pexp + t.e);
-                return ex;
-            };
-            auto touched = [&](const Item& t) __attribute__((always_inline)) {
-                if (t.e != st_e) load_steps(t.e);
-                const int ra = (t.w.rc & 0xffff) * WT_R * 16, ca = (t.w.rc >> 16) * WT_C * 16;   // landmarks
-                return (u_lo < ra + WT_R * 16 && u_hi > ra) || (u_lo < ca + WT_C * 16 && u_hi > ca);
-            };
-            auto skip_of = [&](const Item& t) __attribute__((always_inline)) {
-                const bool tc = touched(t);
-                return tc || (!rz && smask != 0);
-            };
-            auto zero_of = [&](const Item& t) __attribute__((always_inline)) {
-                const bool tc = touched(t);
-                return rz && !tc;
-            };
-            // a wave-tile whose columns all lie past zl is unchanged by the group (its V-side rows
-            // are zero in every step, and no step writes new rows there): not loaded, not stored
-            // (a reset zeroes the block: no skipping then)
-            auto dead = [&](const Item& t) __attribute__((always_inline)) {
-                if (!p.zskip || t.e >= p.E) return false;
-                if (t.e != st_e) load_steps(t.e);
-                return !rz && (t.w.rc >> 16) * WT_C * 16 >= zl;
-            };
-            auto next_live = [&](const Item& c, Item& t) __attribute__((always_inline)) {
-                next_item(c, t);
-                while (t.g < g_end && dead(t)) {
-                    const Item u = t;
-                    next_item(u, t);
-                }
-            };
-            Item cur, nxt, nxt2;
-            bool any_skip = false;
-            first_item(cur);
-            while (cur.g < g_end && dead(cur)) {
-                const Item u = cur;
-                next_item(u, cur);
-            }
-            if (cur.g >= g_end) return;   // (no live wave-tile: nothing to store, no second pass)
-            next_live(cur, nxt);
-            load_tiles(cur);
-            // (the first tiles ahead of every operand load, as in the loop: the wait count at the loop
-            // head then covers the tiles without draining the previous wave-tile's stores)
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < RD - 1; q++) load_ops(q, cur, q);
-            while (true) {
-                const bool more = nxt.g < g_end;
-                next_live(nxt, nxt2);
-                const Item ldi = more ? nxt : cur;   // the last wave-tile re-reads its own rows
-                // a wave-tile holding a landmark some step of the group added, or of an instance whose
-                // σ changes inside the group, is computed here but stored to the sink: the second pass
-                // (below) runs it through the general loop
-                const bool skip = skip_of(cur);
-                const bool zero = zero_of(cur);   // (reset instance, untouched: stored as zero)
-                any_skip |= skip;
-                const int iex = in_exp(cur);
-                const float isc = -ldexpf(1.0f, iex);
-#pragma unroll
-                for (int i = 0; i < WT_N; i++)
-#pragma unroll
-                    for (int qq = 0; qq < 4; qq++)
-#pragma unroll
-                        for (int j = 0; j < 4; j++) acc[i][4 * qq + j] = (float)pref[i][qq][j] * isc;
-                if (!LATE && more) load_tiles(nxt);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int q = 0; q < NS; q++) {
-                    if (LATE && q == TQ && more) load_tiles(nxt);
-                    // ring set of step q + RD − 1 (this wave-tile's, else the next one's)
-                    const int ql = q + RD - 1;
-                    if (ql < NS) load_ops(ql % RD, cur, ql);
-                    else load_ops(ql % RD, ldi, ql - NS);
-                    const int r = q % RD;
-                    if constexpr (F16) {
-                        // (lo, hi), (hi, lo), (hi, hi): 12 MFMAs beside the 8 plane loads
-#pragma unroll
-                        for (int pp = 0; pp < 3; pp++) {
-                            const int pa = pp == 0 ? 1 : 0, pb = pp == 1 ? 1 : 0;
-#pragma unroll
-                            for (int rr = 0; rr < WT_R; rr++)
-#pragma unroll
-                                for (int c = 0; c < WT_C; c++)
-                                    acc[rr * WT_C + c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(
-                                        R[r][rr][pa], R[r][WT_R + c][pb], acc[rr * WT_C + c], 0, 0, 0);
-                        }
-#pragma unroll
-                        for (int i = 0; i < 8; i++) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-                            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read
-                        }
-                        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-                    } else {
-                        // part products smallest first: (mid, mid), (hi, lo), (lo, hi), (hi, mid),
-                        // (mid, hi), (hi, hi)
-#pragma unroll
-                        for (int pp = 0; pp < 6; pp++) {
-                            const int pa = (0x102010 >> (4 * (5 - pp))) & 0xf;
-                            const int pb = (0x120100 >> (4 * (5 - pp))) & 0xf;
-#pragma unroll
-                            for (int rr = 0; rr < WT_R; rr++)
-#pragma unroll
-                                for (int c = 0; c < WT_C; c++)
-                                    acc[rr * WT_C + c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                                        R[r][rr][pa], R[r][WT_R + c][pb], acc[rr * WT_C + c], 0, 0, 0);
-                        }
-#pragma unroll
-                        for (int i = 0; i < 12; i++) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);   // MFMA
-                            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read
-                        }
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                // back from the last step's domain (−1, −2^x, −2^(x − 2σ): an exact power of two, no
-                // division), as whole-vector products (packed multiplies); a zeroed wave-tile (zero is
-                // uniform) takes no multiply at all
-                const float osc = -ldexpf(1.0f, -iex - (F16 ? 2 * (sgl - sg0) : 0));
-                if (zero) {
-#pragma unroll
-                    for (int i = 0; i < WT_N; i++) acc[i] = f32x16{};
-                } else {
-#pragma unroll
-                    for (int i = 0; i < WT_N; i++) acc[i] = acc[i] * osc;
-                }
-                store_tiles(cur, acc, skip);
-                if (!more) break;
-                cur = nxt;
-                nxt = nxt2;
-            }
-            // second pass: the skipped wave-tiles through the general loop (their input tiles are
-            // as read: the first pass stored them to the sink). Exact arithmetic on the fp32 operand
-            // rows there, the split arithmetic elsewhere: both within the fp32 bar (slam_ekf.h)
-            if (any_skip) {
-                Item t;
-                first_item(t);
-                for (int gg = g0; gg < g_end; gg += K) {
-                    if (gg != g0) {
-                        Item nn;
-                        next_item(t, nn);
-                        t = nn;
-                    }
-                    if (!dead(t) && skip_of(t)) wt_general<TS, NS>(p, t.e, t.w, lane);
-                }
-            }
-            return;
-        }
-    } else if (fast) {
-        // raw tile words in flight (fp16 storage: converted when the wave-tile starts)
-        using Raw = typename std::conditional<HALF, f16x4, f32x4>::type;
-        Raw pref[WT_N][4];
-        f32x4 opA[NS][WT_R][2], opB[NS][WT_C][2];
-        f32x16 acc[WT_N];
-        // half h (k-steps 4h..4h+3) of step q's operand rows of wave-tile t, into slot q
-        auto load_half = [&](int slot, const Item& t, int q, int h) __attribute__((always_inline)) {
-            const float* U = op_base(q, 0) + t.e * opstride + lofs + 4 * h;
-            const float* V = op_base(q, 1) + t.e * opstride + lofs + 4 * h;
-            const float us = us_of<TS>(p, t.e);
-#pragma unroll
-            for (int r = 0; r < WT_R; r++)
-                opA[slot][r][h] = *reinterpret_cast<const f32x4*>(U + (size_t)op_row(t, 0, r) * 64 * kh) * us;
-#pragma unroll
-            for (int c = 0; c < WT_C; c++)
-                opB[slot][c][h] = *reinterpret_cast<const f32x4*>(V + (size_t)op_row(t, 1, c) * 64 * kh);
-        };
-        auto load_tiles = [&](const Item& t) __attribute__((always_inline)) {
-#pragma unroll
-            for (int i = 0; i < WT_N; i++) {
-                const Raw* tl = reinterpret_cast<const Raw*>(Pin + tile_ptr(t, i));
-#pragma unroll
-                for (int qq = 0; qq < 4; qq++) pref[i][qq] = __builtin_nontemporal_load(tl + lane + qq * 64);
-            }
-        };
-        // k-steps 4h..4h+3 of step q. Every k-step runs: past the step's matches the scan kernel
-        // leaves (−0)·(+0) operand products, and x + (−0) == x for every x (zeros, NaN, inf too)
-        auto mfma_half = [&](int q, int h) __attribute__((always_inline)) {
-#pragma unroll
-            for (int s = 0; s < 4; s++)
-#pragma unroll
-                for (int r = 0; r < WT_R; r++)
-#pragma unroll
-                    for (int c = 0; c < WT_C; c++)
-                        acc[r * WT_C + c] = __builtin_amdgcn_mfma_f32_32x32x2f32(
-                            opA[q][r][h][s], opB[q][c][h][s], acc[r * WT_C + c], 0, 0, 0);
-        };
-        // one operand load after every group of four MFMAs (4 loads per half step)
-        auto interleave = [&]() __attribute__((always_inline)) {
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);   // MFMA
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read
-            }
-        };
-        Item cur, nxt, nxt2;
-        first_item(cur);
-        next_item(cur, nxt);
-        load_tiles(cur);
-#pragma unroll
-        for (int q = 0; q < NS; q++) {
-            load_half(q, cur, q, 0);
-            load_half(q, cur, q, 1);
-        }
-        int g = g0;
-        while (true) {
-            const bool more = g + K < g_end;
-            next_item(nxt, nxt2);   // read now, used by the next wave-tile
-            // operand rows for the next wave-tile (the last one re-reads its own: no branch
-            // splits the MFMA stream)
-            const Item ldi = more ? nxt : cur;
-#pragma unroll
-            for (int i = 0; i < WT_N; i++)
-#pragma unroll
-                for (int qq = 0; qq < 4; qq++)
-#pragma unroll
-                    for (int j = 0; j < 4; j++) acc[i][4 * qq + j] = (float)pref[i][qq][j];
-            // the next wave-tile's tiles first: the waits of this wave-tile only cover loads issued
-            // during the one before it, so these have the whole wave-tile to land
-            if (more) load_tiles(nxt);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (AM) {
-                // group-major steps (fp16 storage): the
-                // per-step rounding of one group of accumulators runs on the VALU while the other
-                // group's MFMAs run, so it leaves the MFMA stream. Per element the chain is
-                // unchanged (k-ordered step q, then its rounding). Step q's operand registers are
-                // refilled for the next wave-tile during step q+1's first group; the last step's
-                // at the end. (Measured: one accumulator's 8 k-steps back to back, rounding the
-                // previous accumulator beside them, ran 0.84 ms vs 0.79 for the step-major form.)
-                // Pair-major form: group gi = accumulators (gi, 0) and (gi, 1) of the 2 × 2
-                // wave-tile, their k-steps alternating (a dependent MFMA two issues later); the
-                // previous group's 32 elements are rounded 2 per MFMA gap. The last step rounds
-                // group 0 in the first half of group 1 and stores its tiles in the second half.
-                auto mfma_grp = [&](int q, int gi, int pg, bool ld, int lq, bool last) __attribute__((always_inline)) {
-#pragma unroll
-                    for (int m = 0; m < 16; m++) {
-                        const int s = m >> 1, c = m & 1, i = gi * WT_C + c;
-                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(opA[q][gi][s >> 2][s & 3],
-                                                                       opB[q][c][s >> 2][s & 3], acc[i], 0, 0, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (pg >= 0 && !last) {
-                            const int a = pg * WT_C + (m >> 3), k = 2 * (m & 7);
-                            acc[a][k] = round_step<TS>(acc[a][k]);
-                            acc[a][k + 1] = round_step<TS>(acc[a][k + 1]);
-                        }
-                        if (last) {
-                            if (m < 8) {
-                                const int a = pg * WT_C + (m >> 2), k = 4 * (m & 3);
-#pragma unroll
-                                for (int u = 0; u < 4; u++) acc[a][k + u] = round_step<TS>(acc[a][k + u]);
-                            } else {
-                                const int a = pg * WT_C + ((m - 8) >> 2), qq = (m - 8) & 3;
-                                tile_st(((cur.w.valid >> a) & 1) ? Pout + tile_ptr(cur, a) : sink, lane, qq, acc[a]);
-                            }
-                        }
-                        if (ld && (m & 1)) {
-                            // load m/2 of slot lq: half, operand row (A rows, then B rows)
-                            const int l = m >> 1, h = l >> 2, o = l & 3;
-                            const bool isA = o < WT_R;
-                            const float* base = op_base(lq, isA ? 0 : 1) + ldi.e * opstride + lofs + 4 * h;
-                            const f32x4 v = *reinterpret_cast<const f32x4*>(
-                                base + (size_t)op_row(ldi, isA ? 0 : 1, isA ? o : o - WT_R) * 64 * kh);
-                            if (isA) opA[lq][o][h] = v * us_of<TS>(p, ldi.e);
-                            else opB[lq][o - WT_R][h] = v;
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                };
-                static_assert(WT_R == 2 && WT_C == 2, "pair-major form: two groups of two accumulators");
-#pragma unroll
-                for (int q = 0; q < NS; q++) {
-                    mfma_grp(q, 0, q > 0 ? 1 : -1, q > 0, q > 0 ? q - 1 : 0, false);
-                    mfma_grp(q, 1, 0, false, 0, q == NS - 1);
-                }
-#pragma unroll
-                for (int a = 2; a < 4; a++)
-#pragma unroll
-                    for (int k = 0; k < 16; k++) acc[a][k] = round_step<TS>(acc[a][k]);
-                load_half(NS - 1, ldi, NS - 1, 0);
-                load_half(NS - 1, ldi, NS - 1, 1);
-#pragma unroll
-                for (int a = 2; a < 4; a++) {
-                    TS* tl = ((cur.w.valid >> a) & 1) ? Pout + tile_ptr(cur, a) : sink;
-#pragma unroll
-                    for (int qq = 0; qq < 4; qq++) tile_st(tl, lane, qq, acc[a]);
-                }
-                if (!more) break;
-                g += K;
-                cur = nxt;
-                nxt = nxt2;
-                continue;
-            }
-#pragma unroll
-            for (int q = 0; q < NS; q++) {
-                // first half of step q, beside the second half of step q−1's rows for the next
-                // wave-tile (their registers were last read by step q−1)
-                mfma_half(q, 0);
-                if (q > 0) {
-                    load_half(q - 1, ldi, q - 1, 1);
-                    interleave();
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                // second half, beside the first half of step q's rows for the next wave-tile
-                mfma_half(q, 1);
-#pragma unroll
-                for (int i = 0; i < WT_N; i++) round_acc<TS>(acc[i]);
-                load_half(q, ldi, q, 0);
-                interleave();
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            load_half(NS - 1, ldi, NS - 1, 1);
-            store_tiles(cur, acc);
-            if (!more) break;
-            g += K;
-            cur = nxt;
-            nxt = nxt2;
-        }
-        return;
-    }
-
-    // general loop: per wave-tile, every step in order with its operands loaded in place, then
-    // the step's reset or rows (wt_general)
-    Item t;
-    first_item(t);
-    for (int g = g0; g < g_end; g += K) {
-        if (g != g0) {
-            Item n;
-            next_item(t, n);
-            t = n;
-        }
-        wt_general<TS, NS>(p, t.e, t.w, lane);
-    }
-}
-
-// Split-fp16 flush, quad form (EKF_ARITH_F16X3, EKF_OPT_FLUSH_FORM = 44; groups of >= 6 steps).
-// The 2 × 2 wave form streams each wave's 8 KB of operand planes per step through L1/L2 into
-// registers beside its 12 MFMAs, and that stream, not HBM, paces it. Here a
-// workgroup's four MFMA waves take the four wave-tiles of a 2 × 2 group (p.wtq: four entries per
-// group in panel order, entry 2a + b the wave-tile (2R + a, 2C + b); positions wholly below the
-// diagonal or past the block are entries with no stored tile) and share the group's operand row
-// blocks: its 4 A blocks (tile rows) and 4 B blocks (tile columns), both planes, 16 KB per step —
-// half of what the four waves read alone. Loader waves (EKF_Q_LOADERS, no MFMA work) move them by
-// LDS-DMA (global_load_lds_dwordx4, 1 KB per wave-instruction, no register staging) into a ring
-// of D step slots, D − 1 steps ahead of the MFMA waves; one barrier per step: before it each loader
-// waits (its own vmcnt, counted) for the step after the current one to land, and each MFMA wave
-// for its own LDS reads of the current step; after it the MFMA waves read the next step's planes
-// into the second of two register sets while the current step's 12 MFMAs run, and the loaders
-// refill the slot just consumed. The MFMA waves' vector memory queue then holds only their own tile
-// loads (issued EKF_Q_TQ steps into a group for the next one) and stores, so an operand wait never
-// waits for a tile. Per accumulator the chain is the 2 × 2 form's (the same three products per
-// step, in the same order, on the same planes): bit-identical. As there: −P in the accumulators
-// (fp16 storage scaled out of its exponent), the second pass through wt_general for wave-tiles
-// whose steps add rows or whose σ changes, reset instances stored as zero, and a group whose
-// columns all lie past every step's RES_ZMAX skipped whole (dead).
-#ifndef EKF_Q_DEPTH
-#define EKF_Q_DEPTH 8      // quad flush: operand ring slots (16 KB each) = steps in flight
-#endif
-#ifndef EKF_Q_LOADERS
-#define EKF_Q_LOADERS 2    // quad flush: LDS-DMA loader waves beside the four MFMA waves
-#endif
-#ifndef EKF_Q_TQ
-#define EKF_Q_TQ 1         // quad flush: the step of a group at which the next group's tiles are issued
-#endif
-constexpr int Q_WAVES = 4 + EKF_Q_LOADERS;
-constexpr int Q_SLOT = 16 * 1024;   // one step: 8 row blocks × 2 planes × 64 lanes × 16 B
-template <typename TS, int NS>
-__global__ __launch_bounds__(64 * Q_WAVES, 1) void flush_f16q_kernel(DowndateParams p)
-{
-    constexpr int D = EKF_Q_DEPTH < NS ? EKF_Q_DEPTH : NS;
-    constexpr int PPL = 16 / EKF_Q_LOADERS;   // plane pieces per loader wave and step
-    // (vmcnt holds at most 63 outstanding instructions)
-    static_assert(16 % EKF_Q_LOADERS == 0 && D >= 3 && PPL * (D - 2) <= 63, "quad flush: ring");
-    static_assert(NS >= 6 && NS % 2 == 0 && EKF_Q_TQ < NS, "quad flush: step count");
-    constexpr bool HALF = sizeof(TS) == 2;
-    constexpr int NPL = 2;
-    typedef f16x8r f16x8;
-    // the only LDS object: a second one beside a DMA target can make the compiler drain vmcnt
-    // before LDS reads (cdna_hip_programming.md §5)
-    __shared__ __attribute__((aligned(1024))) char ring[D * Q_SLOT];
-
-    const Dims d = p.d;
-    const int ngr = p.nwtq >> 2;   // groups per instance
-    const int total = p.E * ngr;
-    const int per = (total + 7) / 8;   // groups per XCD (a contiguous range)
-    const int xcd = blockIdx.x & 7;
-    const int K = (int)(gridDim.x >> 3);
-    const int g_end = min(total, (xcd + 1) * per);
-    const int gs = xcd * per + (int)(blockIdx.x >> 3);
-    if (gs >= g_end) return;   // (the whole workgroup)
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = threadIdx.x & 63;
-    const size_t inst_elems = (size_t)d.ntiles * TILE_ELEMS;
-    const TS* Pin = reinterpret_cast<const TS*>(p.Pin);
-    TS* Pout = reinterpret_cast<TS*>(p.Pout);
-    TS* sink = reinterpret_cast<TS*>(p.sink);
-
-    // the plain loop needs every step of the workgroup's instances to be a downdate without a
-    // rollback (the 2 × 2 form's fast_rows), decided alike by every wave
-    bool fast_rows = true;
-    {
-        const int e_lo = gs / ngr, e_hi = (g_end - 1) / ngr;
-        for (int e = e_lo; e <= e_hi; e++)
-#pragma unroll
-            for (int q = 0; q < NS; q++)
-                fast_rows = fast_rows && !sload(p.steps[q].res + (size_t)e * RES_STRIDE + RES_ROLLBACK);
-    }
-    struct Grp {
-        int e, gi, g;   // instance, group of the instance, flat index (gs + k·K)
-    };
-    auto first_grp = [&](Grp& t) __attribute__((always_inline)) {
-        t.e = gs / ngr;
-        t.gi = gs - t.e * ngr;
-        t.g = gs;
-    };
-    auto next_grp = [&](const Grp& c, Grp& t) __attribute__((always_inline)) {
-        int gi = c.gi + K, e = c.e;
-        while (gi >= ngr) {
-            gi -= ngr;
-            e++;
-        }
-        t.e = e;
-        t.gi = gi;
-        t.g = c.g + K;
-    };
-    typedef int i32x8 __attribute__((ext_vector_type(8)));
-    static_assert(sizeof(WtEntry) == sizeof(i32x8), "one scalar dwordx8 per entry");
-    auto load_entry = [&](int li, WtEntry& w) __attribute__((always_inline)) {
-        const i32x8 v = sload(reinterpret_cast<const i32x8*>(p.wtq + li));
-#pragma unroll
-        for (int i = 0; i < WT_N; i++) w.tile[i] = v[i];
-        w.valid = v[WT_N];
-        w.rows[0] = v[WT_N + 1];
-        w.rows[1] = v[WT_N + 2];
-        w.rc = v[WT_N + 3];
-    };
-    if (!fast_rows) {   // every wave-tile through the general loop (no LDS, no barriers)
-        if (wv >= 4) return;
-        Grp t;
-        first_grp(t);
-        for (int g = gs; g < g_end; g += K) {
-            if (g != gs) {
-                Grp n;
-                next_grp(t, n);
-                t = n;
-            }
-            WtEntry w;
-            load_entry(4 * t.gi + wv, w);
-            wt_general<TS, NS>(p, t.e, w, lane);
-        }
-        return;
-    }
-
-    // per instance (the 2 × 2 form's bookkeeping): added landmarks [u_lo, u_hi), σ of the first and
-    // last step, σ changes (smask), a reset (rz), the landmarks past every step's RES_ZMAX (zl)
-    auto rec_of = [&](int e, int q, int w) __attribute__((always_inline)) {
-        return sload(p.steps[q].res + (size_t)e * RES_STRIDE + w);
-    };
-    int st_e = -1, u_lo = 0, u_hi = 0, sg0 = 0, sgl = 0, zl = 0;
-    unsigned smask = 0;
-    bool rz = false;
-    auto load_steps = [&](int e) __attribute__((always_inline)) {
-        u_lo = 0x7fffffff;
-        u_hi = 0;
-        smask = 0;
-        rz = false;
-        zl = 0;
-        int prev = 0;
-#pragma unroll
-        for (int q = 0; q < NS; q++) {
-            zl = max(zl, rec_of(e, q, RES_ZMAX));
-            if (rec_of(e, q, RES_RESET)) {
-                u_lo = 0x7fffffff;
-                u_hi = 0;
-                smask = 0;
-                rz = true;
-                continue;
-            }
-            const int na = rec_of(e, q, RES_NADD), s0 = rec_of(e, q, RES_SAVED_IN);
-            if (na > 0) {
-                u_lo = min(u_lo, s0);
-                u_hi = max(u_hi, s0 + na);
-            }
-            const int sg = rec_of(e, q, RES_PSIG);
-            if (q == 0) sg0 = sg;
-            else if (sg != prev) smask |= 1u << (q - 1);
-            if (sg == PLANE_SIGMA_EXACT) smask |= 1u << NS;
-            prev = sg;
-        }
-        sgl = prev;
-        st_e = e;
-    };
-    // a group whose columns all lie past zl (its first wave-tile column, entry 0's): unchanged by
-    // the group's steps, skipped by every wave alike
-    auto dead = [&](const Grp& t) __attribute__((always_inline)) {
-        if (!p.zskip || t.e >= p.E) return false;
-        if (t.e != st_e) load_steps(t.e);
-        const int rc = sload(&p.wtq[4 * t.gi].rc);
-        return !rz && (rc >> 16) * WT_C * 16 >= zl;
-    };
-    auto next_live = [&](const Grp& c, Grp& t) __attribute__((always_inline)) {
-        next_grp(c, t);
-        while (t.g < g_end && dead(t)) {
-            const Grp u = t;
-            next_grp(u, t);
-        }
-    };
-    auto barrier = [&]() __attribute__((always_inline)) {
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    };
-    Grp cur, nxt, nxt2;
-    first_grp(cur);
-    while (cur.g < g_end && dead(cur)) {
-        const Grp u = cur;
-        next_grp(u, cur);
-    }
-    if (cur.g >= g_end) return;   // (uniform: no live group)
-    next_live(cur, nxt);
-
-    if (wv >= 4) {
-        // loader wave: plane pieces LW·PPL .. LW·PPL + PPL − 1 of every step; piece 2·blk + pl is
-        // plane pl of row block blk: blocks 0-3 the group's tile rows (entry 0's A rows, then entry
-        // 3's), 4-7 its tile columns (entry 0's B rows, then entry 3's)
-        const size_t pstride = (size_t)d.nb * NPL * 64;
-        auto pl_base = [&](int q) __attribute__((always_inline)) {
-            int sl = p.slot0 + q;
-            if (sl >= p.nslots) sl -= p.nslots;
-            return reinterpret_cast<const f16x8*>(reinterpret_cast<const char*>(p.bbase) +
-                                                  (size_t)sl * (size_t)p.bslot_bytes);
-        };
-        auto run = [&](auto lwc) __attribute__((always_inline)) {
-            constexpr int LW = decltype(lwc)::value;
-            struct Rows {
-                int w[4];   // entry 0 rows[0], entry 3 rows[0], entry 0 rows[1], entry 3 rows[1]
-            };
-            auto rows_of = [&](const Grp& t, Rows& r) __attribute__((always_inline)) {
-                const int li = 4 * t.gi;
-                r.w[0] = sload(&p.wtq[li].rows[0]);
-                r.w[1] = sload(&p.wtq[li + 3].rows[0]);
-                r.w[2] = sload(&p.wtq[li].rows[1]);
-                r.w[3] = sload(&p.wtq[li + 3].rows[1]);
-            };
-            // step q of group t into ring slot sl
-            auto issue = [&](int sl, const Grp& t, const Rows& r, int q) __attribute__((always_inline)) {
-                const f16x8* b = pl_base(q) + (size_t)t.e * pstride + lane;
-#pragma unroll
-                for (int i = 0; i < PPL; i++) {
-                    const int pc = LW * PPL + i, blk = pc >> 1, pl = pc & 1;
-                    const int row = (r.w[blk >> 1] >> (16 * (blk & 1))) & 0xffff;
-                    __builtin_amdgcn_global_load_lds(
-                        (const void*)(b + ((size_t)row * NPL + pl) * 64),
-                        (__attribute__((address_space(3))) void*)(ring + sl * Q_SLOT + pc * 1024), 16, 0, 0);
-                }
-            };
-            Rows rc, rn;
-            rows_of(cur, rc);
-#pragma unroll
-            for (int s = 0; s < D; s++) issue(s, cur, rc, s);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPL * (D - 1)) : "memory");
-            barrier();
-            int sb = 0;   // ring slot of the group's step 0
-            while (true) {
-                const bool more = nxt.g < g_end;
-                next_live(nxt, nxt2);
-                const Grp ldi = more ? nxt : cur;   // (the last group re-reads its own rows)
-                rows_of(ldi, rn);
-#pragma unroll
-                for (int q = 0; q < NS; q++) {
-                    // step s + 1 landed (the pieces of the D − 2 steps after it may be in flight)
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPL * (D - 2)) : "memory");
-                    barrier();
-                    // step s + D into the slot of step s, which every MFMA wave has read
-                    const int sl = (sb + q) % D;
-                    if (q + D < NS) issue(sl, cur, rc, q + D);
-                    else issue(sl, ldi, rn, q + D - NS);
-                }
-                if (!more) break;
-                sb = (sb + NS) % D;
-                cur = nxt;
-                nxt = nxt2;
-                rc = rn;
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        };
-        if (wv == 4) run(std::integral_constant<int, 0>{});
-#if EKF_Q_LOADERS >= 2
-        else if (wv == 5) run(std::integral_constant<int, 1>{});
-#endif
-#if EKF_Q_LOADERS >= 4
-        else if (wv == 6) run(std::integral_constant<int, 2>{});
-        else if (wv == 7) run(std::integral_constant<int, 3>{});
-#endif
-        return;
-    }
-
-    // MFMA wave (a, b) = (wv >> 1, wv & 1): wave-tile entry 4·gi + wv; its A blocks 2a, 2a + 1
-    // and B blocks 2b, 2b + 1 of the group
-    const int qa = wv >> 1, qb = wv & 1;
-    auto tile_ptr = [&](int e, const WtEntry& w, int i) __attribute__((always_inline)) {
-        return (size_t)e * inst_elems + (size_t)w.tile[i] * TILE_ELEMS;
-    };
-    using Raw = typename std::conditional<HALF, f16x4, f32x4>::type;
-    Raw pref[WT_N][4];
-    f32x16 acc[WT_N];
-    f16x8 op[2][4][NPL];   // [register set][A 2a, A 2a + 1, B 2b, B 2b + 1][hi, lo]
-    auto load_tiles = [&](int e, const WtEntry& w) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < WT_N; i++) {
-            const Raw* tl = reinterpret_cast<const Raw*>(Pin + tile_ptr(e, w, i));
-#pragma unroll
-            for (int qq = 0; qq < 4; qq++) pref[i][qq] = __builtin_nontemporal_load(tl + lane + qq * 64);
-        }
-    };
-    // every slot is stored, the invalid ones to the sink tile (no branch around a store)
-    auto store_tiles = [&](int e, const WtEntry& w, bool skip) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < WT_N; i++) {
-            TS* tl = ((w.valid >> i) & 1) && !skip ? Pout + tile_ptr(e, w, i) : sink;
-#pragma unroll
-            for (int qq = 0; qq < 4; qq++) tile_st(tl, lane, qq, acc[i]);
-        }
-    };
-    const char* rbase = ring + lane * 16;
-    const int aoff = (2 * (2 * qa)) * 1024, boff = (2 * (4 + 2 * qb)) * 1024;
-    auto read_step = [&](int set, int sl) __attribute__((always_inline)) {
-        const char* s = rbase + sl * Q_SLOT;
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int pl = 0; pl < NPL; pl++)
-                op[set][i][pl] = *reinterpret_cast<const f16x8*>(s + (i < 2 ? aoff : boff) + (2 * (i & 1) + pl) * 1024);
-    };
-    auto touched = [&](int e, const WtEntry& w) __attribute__((always_inline)) {
-        if (e != st_e) load_steps(e);
-        const int ra = (w.rc & 0xffff) * WT_R * 16, ca = (w.rc >> 16) * WT_C * 16;
-        return (u_lo < ra + WT_R * 16 && u_hi > ra) || (u_lo < ca + WT_C * 16 && u_hi > ca);
-    };
-    auto skip_of = [&](int e, const WtEntry& w) __attribute__((always_inline)) {
-        return touched(e, w) || (!rz && smask != 0);
-    };
-    // the group's accumulators from its prefetched tiles, −2^iex·P (iex: 2σ of its first step, less
-    // the fp16 storage exponent)
-    auto in_exp = [&](int e) __attribute__((always_inline)) {
-        if (e != st_e) load_steps(e);
-        int ex = 2 * sg0;
-        if constexpr (HALF) ex -= sload(p.pexp + e);
-        return ex;
-    };
-    auto init_acc = [&](int e) __attribute__((always_inline)) {
-        const float isc = -ldexpf(1.0f, in_exp(e));
-#pragma unroll
-        for (int i = 0; i < WT_N; i++)
-#pragma unroll
-            for (int qq = 0; qq < 4; qq++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) acc[i][4 * qq + j] = (float)pref[i][qq][j] * isc;
-    };
-    WtEntry wc, wn;
-    load_entry(4 * cur.gi + wv, wc);
-    load_tiles(cur.e, wc);
-    init_acc(cur.e);
-    bool any_skip = false;
-    barrier();
-    read_step(0, 0);
-    int sb = 0;
-    while (true) {
-        const bool more = nxt.g < g_end;
-        next_live(nxt, nxt2);
-        if (more) load_entry(4 * nxt.gi + wv, wn);
-        const bool skip = skip_of(cur.e, wc);
-        const bool zero = rz && !touched(cur.e, wc);
-        any_skip |= skip;
-        const int iex = in_exp(cur.e);
-        const int sgl_c = sgl, sg0_c = sg0;
-#pragma unroll
-        for (int q = 0; q < NS; q++) {
-            if (q == EKF_Q_TQ && more) load_tiles(nxt.e, wn);
-            barrier();
-            // the next step's planes (this group's, else the next group's first) into the other set
-            read_step((q + 1) & 1, (sb + q + 1) % D);
-            // (the reads ahead of the MFMAs: left to itself the scheduler sinks them below, and the
-            // next step then waits for them)
-            __builtin_amdgcn_sched_barrier(0);
-            const int st = q & 1;
-            // (lo, hi), (hi, lo), (hi, hi) per accumulator, as the 2 × 2 form
-#pragma unroll
-            for (int pp = 0; pp < 3; pp++) {
-                const int pa = pp == 0 ? 1 : 0, pb = pp == 1 ? 1 : 0;
-#pragma unroll
-                for (int rr = 0; rr < WT_R; rr++)
-#pragma unroll
-                    for (int c = 0; c < WT_C; c++)
-                        acc[rr * WT_C + c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(
-                            op[st][rr][pa], op[st][2 + c][pb], acc[rr * WT_C + c], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        const float osc = -ldexpf(1.0f, -iex - 2 * (sgl_c - sg0_c));
-        if (zero) {
-#pragma unroll
-            for (int i = 0; i < WT_N; i++) acc[i] = f32x16{};
-        } else {
-#pragma unroll
-            for (int i = 0; i < WT_N; i++) acc[i] = acc[i] * osc;
-        }
-        store_tiles(cur.e, wc, skip);
-        if (!more) break;
-        sb = (sb + NS) % D;
-        cur = nxt;
-        nxt = nxt2;
-        wc = wn;
-        // (here, behind the stores on every path to it: the wait for the tiles then counts the
-        // stores instead of draining them, as a merge with the first group's path would)
-        init_acc(cur.e);
-    }
-    // second pass: the skipped wave-tiles through the general loop (their input tiles as read: the
-    // first pass stored them to the sink)
-    if (any_skip) {
-        Grp t;
-        first_grp(t);
-        for (int g = gs; g < g_end; g += K) {
-            if (g != gs) {
-                Grp n;
-                next_grp(t, n);
-                t = n;
-            }
-            if (dead(t)) continue;
-            WtEntry w;
-            load_entry(4 * t.gi + wv, w);
-            if (skip_of(t.e, w)) wt_general<TS, NS>(p, t.e, w, lane);
-        }
-    }
-}
-
-// Split-bf16 flush on wave-tiles of 2 × 4 tiles (EKF_ARITH_BF16X6; the default form for its groups).
-// The 2 × 2 form of flush_f32_wave_kernel<TS, NS, true> streams 12 KB of operand planes per step
-// through a CU's vector memory path per wave (3 KB per tile and step: 62 B per clock for the four
-// waves at the MFMA rate) beside its tile stream, and every operand wait of a wave also waits for
-// its older tile loads (one in-order vmcnt). Measured at N = 4096, E = 8, T = 12 (timing builds):
-// MFMA alone 0.36 ms, + operand planes 0.46, + tiles 0.41, both 0.63. A 2 × 4 wave-tile needs 18 KB
-// per step for twice the MFMAs (2.25 KB per tile and step) and amortises each wave-tile's
-// boundary and tile-stream waits over twice the MFMA time. Registers: 8 accumulators (128), the
-// next wave-tile's tiles (128 fp32 / 64 fp16), a ring of 2 operand step-sets (144). Otherwise the
-// 2 × 2 form's scheme: one 4-wave workgroup per CU, barrier-free waves, XCD-ranged K-strided walk
-// of a panel-ordered table (p.wt24: 8 wave-tile columns per panel), tile prefetch one wave-tile
-// ahead, operand ring one step ahead across wave-tile boundaries, −P in the accumulators (fp16:
-// scaled out of the storage exponent), invalid slots stored to the sink. Groups in which some
-// instance of the wave resets or adds rows run wt_general on the two 2 × 2 halves.
-// F16 (EKF_ARITH_F16X3, EKF_OPT_FLUSH_FORM = 24): two fp16 planes of 2^σ·V, three products; the
-// 2 × 2 form then streams 8 KB of planes per wave and step for 12 MFMAs, which at the four waves'
-// MFMA rate is more than a CU's 64 B per clock: 2 × 4 streams 12 KB for 24. Groups whose σ
-// changes run the general halves too.
-constexpr int W4_R = 2, W4_C = 4, W4_N = W4_R * W4_C;
-template <typename TS, int NS, bool F16 = false>
-__global__ __launch_bounds__(DD_THREADS, 1) void flush_bf24_kernel(DowndateParams p)
-{
-    static_assert(NS >= 2 && NS % 2 == 0 && NS <= PMAX, "even step count");
-    constexpr bool HALF = sizeof(TS) == 2;
-    constexpr int NPL = F16 ? 2 : 3;
-    constexpr int RD = (F16 && NS % 4 == 0) ? 4 : 2;   // operand ring depth (divides NS)
-    typedef typename std::conditional<F16, f16x8r, bf16x8r>::type bf16x8;
-    using Raw = typename std::conditional<HALF, f16x4, f32x4>::type;
-    const Dims d = p.d;
-    const int nwt = p.nwt24;
-    const int total = p.E * nwt;
-    const int per = (total + 7) / 8;
-    const int xcd = blockIdx.x & 7;
-    const int K = (int)(gridDim.x >> 3) * (DD_THREADS / 64);     // waves per XCD
-    const int g_end = min(total, (xcd + 1) * per);
-    const int g0 = __builtin_amdgcn_readfirstlane(
-        xcd * per + (int)(blockIdx.x >> 3) * (DD_THREADS / 64) + (int)(threadIdx.x >> 6));
-    if (g0 >= g_end) return;
-    const int lane = threadIdx.x & 63;
-    const int nb = d.nb;
-    const size_t inst_elems = (size_t)d.ntiles * TILE_ELEMS;
-    const TS* Pin = reinterpret_cast<const TS*>(p.Pin);
-    TS* Pout = reinterpret_cast<TS*>(p.Pout);
-    TS* sink = reinterpret_cast<TS*>(p.sink);
-
-    bool fast = true;
-    {
-        const int e_lo = g0 / nwt, e_hi = (g_end - 1) / nwt;
-        for (int e = e_lo; e <= e_hi; e++)
-#pragma unroll
-            for (int q = 0; q < NS; q++) {
-                const int* r = p.steps[q].res + (size_t)e * RES_STRIDE;
-                fast = fast && !sload(r + RES_RESET) && sload(r + RES_NADD) == 0 && !sload(r + RES_ROLLBACK);
-                if (F16) fast = fast && sload(r + RES_PSIG) == sload(p.steps[0].res + (size_t)e * RES_STRIDE + RES_PSIG) &&
-                                sload(r + RES_PSIG) != PLANE_SIGMA_EXACT;
-            }
-    }
-    struct Item {
-        int e, li, wr, wc;
-    };
-    auto load_item = [&](int e, int li, Item& t) __attribute__((always_inline)) {
-        t.e = e;
-        t.li = li;
-        const int v = sload(p.wt24 + (e < p.E ? li : 0));
-        t.wr = v & 0xffff;
-        t.wc = v >> 16;
-    };
-    auto next_item = [&](const Item& c, Item& t) __attribute__((always_inline)) {
-        int li = c.li + K, e = c.e;
-        while (li >= nwt) {
-            li -= nwt;
-            e++;
-        }
-        load_item(e, li, t);
-    };
-    // slot (r, c): tile (2wr + r, 4wc + c) if stored, else a stored tile of the wave-tile
-    auto slot_tile = [&](const Item& t, int i, bool& valid) __attribute__((always_inline)) {
-        const int bi = W4_R * t.wr + i / W4_C, bj = W4_C * t.wc + i % W4_C;
-        valid = bi < nb && bj < nb && bi <= bj;
-        return valid ? tile_index(bi, bj, nb) : tile_index(W4_R * t.wr, min(W4_C * t.wc + W4_C - 1, nb - 1), nb);
-    };
-    auto op_rowA = [&](const Item& t, int r) __attribute__((always_inline)) { return min(W4_R * t.wr + r, nb - 1); };
-    auto op_rowB = [&](const Item& t, int c) __attribute__((always_inline)) { return min(W4_C * t.wc + c, nb - 1); };
-
-    if (!fast) {
-        Item t;
-        load_item(g0 / nwt, g0 - (g0 / nwt) * nwt, t);
-        for (int g = g0; g < g_end; g += K) {
-            if (g != g0) {
-                Item n;
-                next_item(t, n);
-                t = n;
-            }
-#pragma unroll 1
-            for (int h = 0; h < 2; h++) {
-                WtEntry w;
-                w.valid = 0;
-#pragma unroll
-                for (int i = 0; i < WT_N; i++) {
-                    bool v;
-                    w.tile[i] = (int)slot_tile(t, (i / WT_C) * W4_C + 2 * h + i % WT_C, v);
-                    w.valid |= (v ? 1 : 0) << i;
-                }
-                w.rows[0] = op_rowA(t, 0) | (op_rowA(t, 1) << 16);
-                w.rows[1] = op_rowB(t, 2 * h) | (op_rowB(t, 2 * h + 1) << 16);
-                w.rc = t.wr | ((2 * t.wc + h) << 16);
-                wt_general<TS, NS>(p, t.e, w, lane);
-            }
-        }
-        return;
-    }
-
-    const size_t pstride = (size_t)nb * NPL * 64;   // 16-byte operands per instance
-    auto pl_base = [&](int q) __attribute__((always_inline)) {
-        int sl = p.slot0 + q;
-        if (sl >= p.nslots) sl -= p.nslots;
-        return reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(p.bbase) + (size_t)sl * (size_t)p.bslot_bytes);
-    };
-    Raw pref[W4_N][4];
-    f32x16 acc[W4_N];
-    bf16x8 R[RD][W4_R + W4_C][NPL];
-    auto load_ops = [&](int r, const Item& t, int q) __attribute__((always_inline)) {
-        const bf16x8* b = pl_base(q) + t.e * pstride + lane;
-#pragma unroll
-        for (int i = 0; i < W4_R + W4_C; i++) {
-            const bf16x8* rb = b + (size_t)(i < W4_R ? op_rowA(t, i) : op_rowB(t, i - W4_R)) * NPL * 64;
-#pragma unroll
-            for (int pl = 0; pl < NPL; pl++) R[r][i][pl] = rb[pl * 64];
-        }
-    };
-    auto load_tiles = [&](const Item& t) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < W4_N; i++) {
-            bool v;
-            const Raw* tl = reinterpret_cast<const Raw*>(Pin + (size_t)t.e * inst_elems + (size_t)slot_tile(t, i, v) * TILE_ELEMS);
-#pragma unroll
-            for (int qq = 0; qq < 4; qq++) pref[i][qq] = __builtin_nontemporal_load(tl + lane + qq * 64);
-        }
-    };
-    // −P in the accumulators, scaled: fp16 storage out of its exponent x, F16 by 2^(2σ) (the
-    // group's one σ): −2^(2σ − x)
-    auto in_scale = [&](const Item& t) __attribute__((always_inline)) {
-        int ex = F16 ? 2 * sload(p.steps[0].res + (size_t)t.e * RES_STRIDE + RES_PSIG) : 0;
-        if constexpr (HALF) ex -= sload(p.pexp + t.e);
-        return -ldexpf(1.0f, ex);
-    };
-    Item cur, nxt, nxt2;
-    load_item(g0 / nwt, g0 - (g0 / nwt) * nwt, cur);
-    next_item(cur, nxt);
-    load_tiles(cur);
-#pragma unroll
-    for (int q = 0; q < RD - 1; q++) load_ops(q, cur, q);
-    int g = g0;
-    while (true) {
-        const bool more = g + K < g_end;
-        next_item(nxt, nxt2);
-        const Item ldi = more ? nxt : cur;   // the last wave-tile re-reads its own rows
-        const float isc = in_scale(cur);
-#pragma unroll
-        for (int i = 0; i < W4_N; i++)
-#pragma unroll
-            for (int qq = 0; qq < 4; qq++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) acc[i][4 * qq + j] = (float)pref[i][qq][j] * isc;
-        if (more) load_tiles(nxt);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < NS; q++) {
-            const int ql = q + RD - 1;
-            if (ql < NS) load_ops(ql % RD, cur, ql);
-            else load_ops(ql % RD, ldi, ql - NS);
-            const int r = q % RD;
-            if constexpr (F16) {
-                // (lo, hi), (hi, lo), (hi, hi): 24 MFMAs beside the 12 plane loads
-#pragma unroll
-                for (int pp = 0; pp < 3; pp++) {
-                    const int pa = pp == 0 ? 1 : 0, pb = pp == 1 ? 1 : 0;
-#pragma unroll
-                    for (int rr = 0; rr < W4_R; rr++)
-#pragma unroll
-                        for (int c = 0; c < W4_C; c++)
-                            acc[rr * W4_C + c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(
-                                R[r][rr][pa], R[r][W4_R + c][pb], acc[rr * W4_C + c], 0, 0, 0);
-                }
-#pragma unroll
-                for (int i = 0; i < 12; i++) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);   // MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read
-                }
-            } else {
-                // part products smallest first: (mid, mid), (hi, lo), (lo, hi), (hi, mid), (mid, hi), (hi, hi)
-#pragma unroll
-                for (int pp = 0; pp < 6; pp++) {
-                    const int pa = (0x102010 >> (4 * (5 - pp))) & 0xf;
-                    const int pb = (0x120100 >> (4 * (5 - pp))) & 0xf;
-#pragma unroll
-                    for (int rr = 0; rr < W4_R; rr++)
-#pragma unroll
-                        for (int c = 0; c < W4_C; c++)
-                            acc[rr * W4_C + c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                                R[r][rr][pa], R[r][W4_R + c][pb], acc[rr * W4_C + c], 0, 0, 0);
-                }
-#pragma unroll
-                for (int i = 0; i < 6; i++) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);   // MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x020, 3, 0);   // VMEM read
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        const float osc = 1.0f / isc;   // (a power of two: exact)
-#pragma unroll
-        for (int i = 0; i < W4_N; i++) {
-            bool v;
-            const size_t ti = slot_tile(cur, i, v);
-            TS* tl = v ? Pout + (size_t)cur.e * inst_elems + ti * TILE_ELEMS : sink;
-#pragma unroll
-            for (int k = 0; k < 16; k++) acc[i][k] = acc[i][k] * osc;
-#pragma unroll
-            for (int qq = 0; qq < 4; qq++) tile_st(tl, lane, qq, acc[i]);
-        }
-        if (!more) break;
-        g += K;
-        cur = nxt;
-        nxt = nxt2;
-    }
-}
-
-// f64 flush, barrier-free per-wave form for groups of NS <= F64_WAVE_MAXS steps (kmax == 16):
-// the f32 wave kernel's scheme at fp64. One wave per SIMD walks wave-tiles of 1 × 2 tiles (eight
-// 16×16 v_mfma_f64_16x16x4_f64 accumulators, 64 registers); while wave-tile k runs its NS × 32
-// MFMAs, the tiles of wave-tile k+1 (issued first) and, step by step, its operand rows stream
-// into registers. fp64 is HBM-bound at T = 4 (8 B per element: 0.54 ms of traffic vs 0.44 ms of
-// MFMA per launch at E = 8, N = 4096), so the wave keeps a whole wave-tile of loads in flight.
-// Every k-step runs (the scan pads the operands past the matches with −0·(+0)); per element the
-// chain is that of downdate_f64_kernel and of the on-read replay: bit-identical results. Groups
-// with a reset or augmented rows for the wave's instances take a plain per-wave-tile loop.
-template <int NS>
-__global__ __launch_bounds__(DD_THREADS, 1) void flush_f64_wave_kernel(DowndateParams p)
-{
-    static_assert(NS >= 1 && NS <= F64_WAVE_MAXS, "steps per launch");
-    const Dims d = p.d;
-    const int nwt = p.nwt64;
-    const int total = p.E * nwt;
-    const int per = (total + 7) / 8;
-    const int xcd = blockIdx.x & 7;
-    const int K = (int)(gridDim.x >> 3) * (DD_THREADS / 64);     // waves per XCD
-    const int g_end = min(total, (xcd + 1) * per);
-    const int g0 = __builtin_amdgcn_readfirstlane(
-        xcd * per + (int)(blockIdx.x >> 3) * (DD_THREADS / 64) + (int)(threadIdx.x >> 6));
-    if (g0 >= g_end) return;
-    const int lane = threadIdx.x & 63;
-    const int kh = d.kmax / 2;   // doubles per lane per row block (2 halves × kmax/4)
-    const int kq = d.kmax / 4;
-    const size_t opstride = (size_t)d.nb * 64 * kh;
-    const size_t inst_elems = (size_t)d.ntiles * TILE_ELEMS;
-    const double* Pin = reinterpret_cast<const double*>(p.Pin);
-    double* Pout = reinterpret_cast<double*>(p.Pout);
-
-    bool fast = d.kmax == 16;
-    {
-        const int e_lo = g0 / nwt, e_hi = (g_end - 1) / nwt;
-        for (int e = e_lo; e <= e_hi; e++)
-#pragma unroll
-            for (int q = 0; q < NS; q++) {
-                const int* r = p.steps[q].res + (size_t)e * RES_STRIDE;
-                fast = fast && !sload(r + RES_RESET) && sload(r + RES_NADD) == 0 && !sload(r + RES_ROLLBACK);
-            }
-    }
-    struct Item {
-        int e, li;
-        int tile[WT64_C];
-        int valid, rowA, rowsB;
-    };
-    typedef int i32x8 __attribute__((ext_vector_type(8)));
-    auto load_entry = [&](int li, Item& t) __attribute__((always_inline)) {
-        const i32x8 v = sload(reinterpret_cast<const i32x8*>(p.wt64 + li));
-        t.tile[0] = v[0];
-        t.tile[1] = v[1];
-        t.valid = v[WT_N];
-        t.rowA = v[WT_N + 1];
-        t.rowsB = v[WT_N + 2];
-    };
-    auto first_item = [&](Item& t) __attribute__((always_inline)) {
-        t.e = g0 / nwt;
-        t.li = g0 - t.e * nwt;
-        load_entry(t.li, t);
-    };
-    auto next_item = [&](const Item& c, Item& t) __attribute__((always_inline)) {
-        int li = c.li + K, e = c.e;
-        while (li >= nwt) {
-            li -= nwt;
-            e++;
-        }
-        t.e = e;
-        t.li = li;
-        load_entry(e < p.E ? li : 0, t);
-    };
-    auto tile_base = [&](const Item& t, int i) __attribute__((always_inline)) {
-        return (size_t)t.e * inst_elems + (size_t)t.tile[i] * TILE_ELEMS;
-    };
-    // lane's registers 0-1 of 16×16 block b of a tile at f64x2 b·128 + lane, 2-3 at b·128 + 64 + lane
-    auto load_tiles = [&](const Item& t, f64x2 (&pref)[WT64_C][8]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < WT64_C; i++) {
-            const f64x2* src = reinterpret_cast<const f64x2*>(Pin + tile_base(t, i)) + lane;
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                pref[i][2 * b] = __builtin_nontemporal_load(src + b * 128);
-                pref[i][2 * b + 1] = __builtin_nontemporal_load(src + b * 128 + 64);
-            }
-        }
-    };
-    // invalid slots to the sink tile (no branch around a store: see flush_f32_wave_kernel)
-    auto store_tiles = [&](const Item& t, const f64x4 (&acc)[WT64_C][4]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < WT64_C; i++) {
-            f64x2* dst = reinterpret_cast<f64x2*>(((t.valid >> i) & 1) ? Pout + tile_base(t, i)
-                                                                      : reinterpret_cast<double*>(p.sink)) + lane;
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                const f64x2 v0 = {acc[i][b][0], acc[i][b][1]};
-                const f64x2 v1 = {acc[i][b][2], acc[i][b][3]};
-                __builtin_nontemporal_store(v0, dst + b * 128);
-                __builtin_nontemporal_store(v1, dst + b * 128 + 64);
-            }
-        }
-    };
-    // operand rows of step q for wave-tile t: A (its row block), B (its two column blocks), each
-    // 8 doubles per lane ([half h][k-step s] at h·kq + s)
-    auto load_ops = [&](const Item& t, int q, f64x2 (&a)[4], f64x2 (&b)[WT64_C][4]) __attribute__((always_inline)) {
-        const double* U = reinterpret_cast<const double*>(p.steps[q].Uop) + t.e * opstride + lane * kh;
-        const double* V = reinterpret_cast<const double*>(p.steps[q].Vop) + t.e * opstride + lane * kh;
-        const f64x2* ua = reinterpret_cast<const f64x2*>(U + (size_t)t.rowA * 64 * kh);
-#pragma unroll
-        for (int k = 0; k < 4; k++) a[k] = ua[k];
-#pragma unroll
-        for (int c = 0; c < WT64_C; c++) {
-            const int rb = (t.rowsB >> (16 * c)) & 0xffff;
-            const f64x2* vb = reinterpret_cast<const f64x2*>(V + (size_t)rb * 64 * kh);
-#pragma unroll
-            for (int k = 0; k < 4; k++) b[c][k] = vb[k];
-        }
-    };
-    // the 4 k-steps of one step: acc[c][h·2 + hc] += A[h] · B[c][hc]
-    auto mfma_step = [&](const f64x2 (&a)[4], const f64x2 (&b)[WT64_C][4], f64x4 (&acc)[WT64_C][4]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int s4 = 0; s4 < 4; s4++) {
-            const double a0 = a[s4 >> 1][s4 & 1], a1 = a[2 + (s4 >> 1)][s4 & 1];
-#pragma unroll
-            for (int c = 0; c < WT64_C; c++) {
-                const double b0 = b[c][s4 >> 1][s4 & 1], b1 = b[c][2 + (s4 >> 1)][s4 & 1];
-                acc[c][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[c][0], 0, 0, 0);
-                acc[c][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[c][1], 0, 0, 0);
-                acc[c][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[c][2], 0, 0, 0);
-                acc[c][3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[c][3], 0, 0, 0);
-            }
-        }
-    };
-    auto to_acc = [&](const f64x2 (&pref)[WT64_C][8], f64x4 (&acc)[WT64_C][4]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < WT64_C; i++)
-#pragma unroll
-            for (int b = 0; b < 4; b++)
-                acc[i][b] = f64x4{pref[i][2 * b][0], pref[i][2 * b][1], pref[i][2 * b + 1][0], pref[i][2 * b + 1][1]};
-    };
-
-    if (fast) {
-        // operand ring of RD steps: step q + RD's rows load into step q's registers after its
-        // MFMAs (the next wave-tile's once q + RD >= NS; RD = NS up to four steps)
-        constexpr int RD = NS < F64_RING ? NS : F64_RING;
-        f64x2 pref[WT64_C][8];
-        f64x2 opa[RD][4], opb[RD][WT64_C][4];
-        f64x4 acc[WT64_C][4];
-        Item cur, nxt, nxt2;
-        first_item(cur);
-        next_item(cur, nxt);
-        load_tiles(cur, pref);
-#pragma unroll
-        for (int q = 0; q < RD; q++) load_ops(cur, q, opa[q], opb[q]);
-        int g = g0;
-        while (true) {
-            const bool more = g + K < g_end;
-            next_item(nxt, nxt2);
-            const Item ldi = more ? nxt : cur;   // the last wave-tile re-reads its own (no branch)
-            to_acc(pref, acc);
-            if (more) load_tiles(nxt, pref);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < NS; q++) {
-                mfma_step(opa[q % RD], opb[q % RD], acc);
-                __builtin_amdgcn_sched_barrier(0);
-                if (q + RD < NS) load_ops(cur, q + RD, opa[q % RD], opb[q % RD]);
-                else load_ops(ldi, q + RD - NS, opa[q % RD], opb[q % RD]);   // the next wave-tile's
-            }
-            store_tiles(cur, acc);
-            if (!more) break;
-            g += K;
-            cur = nxt;
-            nxt = nxt2;
-        }
-        return;
-    }
-
-    // general loop: per wave-tile, every step in order (reset, or the k-steps of its matches, then
-    // its augmented rows), operands loaded in place
-    Item t;
-    first_item(t);
-    for (int g = g0; g < g_end; g += K) {
-        if (g != g0) {
-            Item n;
-            next_item(t, n);
-            t = n;
-        }
-        f64x2 pref[WT64_C][8];
-        f64x4 acc[WT64_C][4];
-        load_tiles(t, pref);
-        to_acc(pref, acc);
-        const int wc0 = (t.rowsB & 0xffff);
-        for (int q = 0; q < NS; q++) {
-            const int* r = p.steps[q].res + (size_t)t.e * RES_STRIDE;
-            if (sload(r + RES_RESET)) {
-#pragma unroll
-                for (int i = 0; i < WT64_C; i++)
-#pragma unroll
-                    for (int b = 0; b < 4; b++) acc[i][b] = f64x4{0.0, 0.0, 0.0, 0.0};
-                continue;
-            }
-            const int ks = sload(r + RES_KSTEPS);
-            if (ks > 0) {
-                const double* U = reinterpret_cast<const double*>(p.steps[q].Uop) + t.e * opstride + lane * kh;
-                const double* V = reinterpret_cast<const double*>(p.steps[q].Vop) + t.e * opstride + lane * kh;
-                const double* A = U + (size_t)t.rowA * 64 * kh;
-                for (int s4 = 0; s4 < ks; s4++) {
-                    const double a0 = A[s4], a1 = A[kq + s4];
-#pragma unroll
-                    for (int c = 0; c < WT64_C; c++) {
-                        const double* B = V + (size_t)((t.rowsB >> (16 * c)) & 0xffff) * 64 * kh;
-                        const double b0 = B[s4], b1 = B[kq + s4];
-                        acc[c][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[c][0], 0, 0, 0);
-                        acc[c][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[c][1], 0, 0, 0);
-                        acc[c][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[c][2], 0, 0, 0);
-                        acc[c][3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[c][3], 0, 0, 0);
-                    }
-                }
-            }
-            const int nadd = sload(r + RES_NADD), s0 = sload(r + RES_SAVED_IN);
-            if (nadd <= 0 || (wc0 + WT64_C) * 16 <= s0 || wc0 * 16 >= s0 + nadd) continue;
-            const double* prw0 = p.steps[q].patch + (size_t)t.e * d.max_lines * 2 * d.M;
-            const double* pdg = p.steps[q].patch_diag + (size_t)t.e * d.max_lines * 4;
-#pragma unroll
-            for (int c = 0; c < WT64_C; c++) {
-                const int bj = wc0 + c;
-                if (!((t.valid >> c) & 1) || bj * 16 + 15 < s0 || bj * 16 >= s0 + nadd) continue;
-#pragma unroll
-                for (int blk = 0; blk < 4; blk++)
-#pragma unroll
-                    for (int reg = 0; reg < 4; reg++) {
-                        const int row = t.rowA * 32 + (lane >> 4) + 4 * reg + 16 * (blk >> 1);
-                        const int col = bj * 32 + (lane & 15) + 16 * (blk & 1);
-                        const int hi = max(row >> 1, col >> 1);
-                        if (hi >= s0 && hi < s0 + nadd) acc[c][blk][reg] = patched_value(prw0, pdg, d.M, s0, row, col);
-                    }
-            }
-        }
-        store_tiles(t, acc);
-    }
-}
-
-#if !defined(EKF_TU) || EKF_TU == 2   // (a plain kernel: defined in the flush unit only)
-__global__ __launch_bounds__(DD_THREADS) void downdate_f64_kernel(DowndateParams p)
-{
-    const Dims d = p.d;
-    const int lane = threadIdx.x & 63;
-    const int64_t nwaves = (int64_t)gridDim.x * (DD_THREADS / 64);
-    const int64_t total = (int64_t)p.E * d.ntiles;
-    const int kh = d.kmax / 2;   // doubles per lane per row block (2 halves × kmax/4)
-    const int kq = d.kmax / 4;
-    const size_t opstride = (size_t)d.nb * 64 * kh;
-    for (int64_t g = (int64_t)blockIdx.x * (DD_THREADS / 64) + (threadIdx.x >> 6); g < total;
-         g += nwaves) {
-        const int e = (int)(g / d.ntiles);
-        const int64_t t = g - (int64_t)e * d.ntiles;
-        const size_t toff = ((size_t)e * d.ntiles + t) * TILE_ELEMS;
-        // lane's registers 0-1 of block qq at qq·128 + lane, registers 2-3 at qq·128 + 64 + lane
-        const f64x2* src = reinterpret_cast<const f64x2*>(reinterpret_cast<const double*>(p.Pin) + toff) + lane;
-        f64x2* dst = reinterpret_cast<f64x2*>(reinterpret_cast<double*>(p.Pout) + toff) + lane;
-        const int2 rc = p.tile_rc[t];
-        bool work = false;
-        for (int q = 0; q < p.nsteps; q++) {
-            const int* r = p.steps[q].res + (size_t)e * RES_STRIDE;
-            const int nadd = r[RES_NADD], s0 = r[RES_SAVED_IN];
-            work |= r[RES_RESET] || r[RES_KSTEPS] > 0 ||
-                    (nadd > 0 && rc.y * 16 + 15 >= s0 && rc.y * 16 < s0 + nadd);
-        }
-        if (!work) {
-            if (p.Pin != p.Pout) {
-#pragma unroll
-                for (int qq = 0; qq < 4; qq++) {
-                    __builtin_nontemporal_store(__builtin_nontemporal_load(src + qq * 128), dst + qq * 128);
-                    __builtin_nontemporal_store(__builtin_nontemporal_load(src + qq * 128 + 64), dst + qq * 128 + 64);
-                }
-            }
-            continue;
-        }
-        f64x4 acc[4];
-#pragma unroll
-        for (int qq = 0; qq < 4; qq++) {
-            const f64x2 v0 = __builtin_nontemporal_load(src + qq * 128);
-            const f64x2 v1 = __builtin_nontemporal_load(src + qq * 128 + 64);
-            acc[qq][0] = v0[0];
-            acc[qq][1] = v0[1];
-            acc[qq][2] = v1[0];
-            acc[qq][3] = v1[1];
-        }
-        for (int q = 0; q < p.nsteps; q++) {
-            const Slot& sq = p.steps[q];
-            const int* r = sq.res + (size_t)e * RES_STRIDE;
-            if (r[RES_RESET]) {
-#pragma unroll
-                for (int qq = 0; qq < 4; qq++) acc[qq] = f64x4{0.0, 0.0, 0.0, 0.0};
-                continue;
-            }
-            const int ks = r[RES_KSTEPS];
-            if (ks > 0) {
-                const double* A = reinterpret_cast<const double*>(sq.Uop) + e * opstride +
-                                  ((size_t)rc.x * 64 + lane) * kh;
-                const double* B = reinterpret_cast<const double*>(sq.Vop) + e * opstride +
-                                  ((size_t)rc.y * 64 + lane) * kh;
-                for (int s = 0; s < ks; s++) {
-                    const double a0 = A[s], a1 = A[kq + s];
-                    const double b0 = B[s], b1 = B[kq + s];
-                    acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[1], 0, 0, 0);
-                    acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[2], 0, 0, 0);
-                    acc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[3], 0, 0, 0);
-                }
-            }
-            const int nadd = r[RES_NADD], s0 = r[RES_SAVED_IN];
-            if (nadd > 0 && rc.y * 16 + 15 >= s0 && rc.y * 16 < s0 + nadd) {
-                const double* prw0 = sq.patch + (size_t)e * d.max_lines * 2 * d.M;
-                const double* pdg = sq.patch_diag + (size_t)e * d.max_lines * 4;
-#pragma unroll
-                for (int blk = 0; blk < 4; blk++)
-#pragma unroll
-                    for (int reg = 0; reg < 4; reg++) {
-                        const int row = rc.x * 32 + (lane >> 4) + 4 * reg + 16 * (blk >> 1);
-                        const int col = rc.y * 32 + (lane & 15) + 16 * (blk & 1);
-                        const int hi = max(row >> 1, col >> 1);
-                        if (hi >= s0 && hi < s0 + nadd)
-                            acc[blk][reg] = patched_value(prw0, pdg, d.M, s0, row, col);
-                    }
-            }
-        }
-#pragma unroll
-        for (int qq = 0; qq < 4; qq++) {
-            const f64x2 v0 = {acc[qq][0], acc[qq][1]};
-            const f64x2 v1 = {acc[qq][2], acc[qq][3]};
-            __builtin_nontemporal_store(v0, dst + qq * 128);
-            __builtin_nontemporal_store(v1, dst + qq * 128 + 64);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// state transfer / initialisation
-// ---------------------------------------------------------------------------------------
-#endif
-
-template <typename T>
-__device__ __forceinline__ void tile_rc_of(int rem, int& r, int& c)
-{
-    if (sizeof(typename Stor<T>::L) == 4) {
-        const int q = rem & 3, lane = (rem >> 2) & 63, grp = rem >> 8;
-        c = lane & 31;
-        r = q + 4 * (lane >> 5) + 8 * grp;
-    } else {
-        const int reg = (rem & 1) + 2 * ((rem >> 7) & 1), lane = (rem >> 1) & 63, blk = rem >> 8;
-        c = (lane & 15) + 16 * (blk & 1);
-        r = (lane >> 4) + 4 * reg + 16 * (blk >> 1);
-    }
-}
-
-// pack / unpack / lowrank cover the tiles [t0, t1) (a partitioned instance stores a slice; Pll points
-// at the slice's first tile, t0)
-template <typename T>
-__global__ void pack_kernel(Dims d, const double* __restrict__ Pfull, T* __restrict__ Pll,
-                            double* __restrict__ Rs, const int2* __restrict__ tile_rc, int ex,
-                            int64_t t0, int64_t t1)
-{
-    const int64_t total = (t1 - t0) * TILE_ELEMS;
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total;
-         g += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t t = t0 + g / TILE_ELEMS;
-        int r, c;
-        tile_rc_of<T>((int)(g % TILE_ELEMS), r, c);
-        const int2 rc = tile_rc[t];
-        const int i = rc.x * TILE + r, j = rc.y * TILE + c;
-        double v = 0.0;
-        if (i < d.M && j < d.M) v = Pfull[(size_t)(3 + i) * d.n + (3 + j)];
-        Pll[g] = to_store<T>(to_domain<T>(v, ex));
-    }
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < 3 * (int64_t)d.n;
-         g += (int64_t)gridDim.x * blockDim.x) {
-        const int a = (int)(g / d.n), b = (int)(g % d.n);
-        Rs[g] = Pfull[(size_t)a * d.n + b];
-    }
-}
-
-template <typename T>
-__global__ void unpack_kernel(Dims d, double* __restrict__ Pfull, const T* __restrict__ Pll,
-                              const double* __restrict__ Rs, int ex, int64_t t0, int64_t t1)
-{
-    const int64_t total = (int64_t)d.n * d.n;
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total;
-         g += (int64_t)gridDim.x * blockDim.x) {
-        const int a = (int)(g / d.n), b = (int)(g % d.n);
-        double v;
-        if (a < 3) v = Rs[(size_t)a * d.n + b];
-        else if (b < 3) v = Rs[(size_t)b * d.n + a];
-        else {
-            // the tiles of another rank read as 0
-            const int ba = (a - 3) >> 5, bb = (b - 3) >> 5;
-            const int64_t t = tile_index(ba < bb ? ba : bb, ba < bb ? bb : ba, d.nb);
-            v = (t >= t0 && t < t1)
-                    ? from_domain<T>(from_store<T>(Pll[ll_offset<typename Stor<T>::L>(a - 3, b - 3, d.nb) - t0 * TILE_ELEMS]), ex)
-                    : 0.0;
-        }
-        Pfull[g] = v;
-    }
-}
-
-template <typename T>
-__global__ void lowrank_kernel(Dims d, const double* __restrict__ diag,
-                               const double* __restrict__ U, int rank, T* __restrict__ Pll,
-                               double* __restrict__ Rs, const int2* __restrict__ tile_rc, int ex,
-                               int64_t t0, int64_t t1)
-{
-    const int64_t total = (t1 - t0) * TILE_ELEMS;
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total;
-         g += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t t = t0 + g / TILE_ELEMS;
-        int r, c;
-        tile_rc_of<T>((int)(g % TILE_ELEMS), r, c);
-        const int2 rc = tile_rc[t];
-        const int i = rc.x * TILE + r, j = rc.y * TILE + c;
-        double v = 0.0;
-        if (i < d.M && j < d.M) {
-            const double* ui = U + (size_t)(3 + i) * rank;
-            const double* uj = U + (size_t)(3 + j) * rank;
-            for (int k = 0; k < rank; k++) v += ui[k] * uj[k];
-            if (i == j) v += diag[3 + i];
-        }
-        Pll[g] = to_store<T>(to_domain<T>(v, ex));
-    }
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < 3 * (int64_t)d.n;
-         g += (int64_t)gridDim.x * blockDim.x) {
-        const int a = (int)(g / d.n), b = (int)(g % d.n);
-        const double* ua = U + (size_t)a * rank;
-        const double* ub = U + (size_t)b * rank;
-        double v = 0.0;
-        for (int k = 0; k < rank; k++) v += ua[k] * ub[k];
-        if (a == b) v += diag[a];
-        Rs[g] = v;
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// launchers
-// ---------------------------------------------------------------------------------------
-// The association kernel on 128 / 64 landmarks per workgroup (ScanParams::nt): its HOT
-// instantiations (symmetric fp32 operands, kmax = 16; HOT = 2 split-fp16, 1 the others), one
-// compilation unit per width (EKF_TU 7, 8)
-hipError_t launch_scan_nt128(const ScanParams& p, bool half, bool f16x3, hipStream_t st);
-hipError_t launch_scan_nt64(const ScanParams& p, bool half, bool f16x3, hipStream_t st);
-
-#if !defined(EKF_TU) || EKF_TU == 7
-hipError_t launch_scan_nt128(const ScanParams& p, bool half, bool f16x3, hipStream_t st)
-{
-    const dim3 grid(p.G * p.E), block(128 + 64);
-    if (f16x3) {
-        if (half) hipLaunchKernelGGL((scan_kernel<_Float16, false, 2, 128>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_kernel<float, false, 2, 128>), grid, block, 0, st, p);
-    } else {
-        if (half) hipLaunchKernelGGL((scan_kernel<_Float16, false, 1, 128>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_kernel<float, false, 1, 128>), grid, block, 0, st, p);
-    }
-    return hipGetLastError();
-}
-#endif
-
-#if !defined(EKF_TU) || EKF_TU == 8
-hipError_t launch_scan_nt64(const ScanParams& p, bool half, bool f16x3, hipStream_t st)
-{
-    const dim3 grid(p.G * p.E), block(64 + 64);
-    if (f16x3) {
-        if (half) hipLaunchKernelGGL((scan_kernel<_Float16, false, 2, 64>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_kernel<float, false, 2, 64>), grid, block, 0, st, p);
-    } else {
-        if (half) hipLaunchKernelGGL((scan_kernel<_Float16, false, 1, 64>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_kernel<float, false, 1, 64>), grid, block, 0, st, p);
-    }
-    return hipGetLastError();
-}
-#endif
-
-#if !defined(EKF_TU) || EKF_TU == 1
-int scan_blocks_per_cu(int precision)
-{
-    int nb = 0;
-    hipError_t err =
-        (precision == EKF_PREC_F64) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, scan_kernel<double, false, 0>, SCAN_BLOCK, 0)
-        : (precision == EKF_PREC_F16) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, scan_kernel<_Float16, false, 0>, SCAN_BLOCK, 0)
-        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, scan_kernel<float, false, 0>, SCAN_BLOCK, 0);
-    return err == hipSuccess ? nb : 0;
-}
-
-size_t scan_lds_bytes(int precision)
-{
-    hipFuncAttributes a;
-    hipError_t err =
-        (precision == EKF_PREC_F64) ? hipFuncGetAttributes(&a, reinterpret_cast<const void*>(scan_kernel<double, false, 0>))
-        : (precision == EKF_PREC_F16) ? hipFuncGetAttributes(&a, reinterpret_cast<const void*>(scan_kernel<_Float16, false, 0>))
-        : hipFuncGetAttributes(&a, reinterpret_cast<const void*>(scan_kernel<float, false, 0>));
-    return err == hipSuccess ? a.sharedSizeBytes : 0;
-}
-
-#endif
-
-#if !defined(EKF_TU) || EKF_TU == 3
-hipError_t launch_shard_run(const ShardParams& p, int precision, hipStream_t st)
-{
-    const unsigned G = (unsigned)shard_run_workgroups(p.d.N);
-    // at most SH_MAX_LINES lines: one verdict exchange for the run (shard_spec_kernel); otherwise
-    // one exchange per line (shard_run_kernel)
-    if (EKF_SHARD_SPEC && p.L <= SH_MAX_LINES && p.d.max_lines <= SH_MAX_LINES) {
-        if (precision == EKF_PREC_F64) hipLaunchKernelGGL(shard_spec_kernel<double>, dim3(G), dim3(SPR_THREADS), 0, st, p);
-        else if (precision == EKF_PREC_F32) hipLaunchKernelGGL(shard_spec_kernel<float>, dim3(G), dim3(SPR_THREADS), 0, st, p);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-    }
-    if (precision == EKF_PREC_F64) hipLaunchKernelGGL(shard_run_kernel<double>, dim3(G), dim3(SHR_THREADS), 0, st, p);
-    else if (precision == EKF_PREC_F32) hipLaunchKernelGGL(shard_run_kernel<float>, dim3(G), dim3(SHR_THREADS), 0, st, p);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-hipError_t launch_shard(const ShardParams& p, int precision, hipStream_t st)
-{
-    // every landmark, one per thread, spread over ⌈N/64⌉ CUs
-    // (the guesses and the guessed columns: one grid row per line)
-    const bool per_line = p.phase == SH_SPEC_COLS || p.phase == SH_GUESS;
-    const dim3 grid((unsigned)((p.d.N + SH_THREADS - 1) / SH_THREADS), per_line ? (unsigned)max(p.L, 1) : 1u);
-    if (precision == EKF_PREC_F64) hipLaunchKernelGGL(shard_kernel<double>, grid, dim3(SH_THREADS), 0, st, p);
-    else if (precision == EKF_PREC_F32) hipLaunchKernelGGL(shard_kernel<float>, grid, dim3(SH_THREADS), 0, st, p);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-#endif
-
-#if !defined(EKF_TU) || EKF_TU == 1
-hipError_t launch_scan(const ScanParams& p, int precision, hipStream_t st)
-{
-    if (p.nt != SCAN_THREADS) {   // (the context picks a narrow width for the HOT instantiations only)
-        if (p.dbg || precision == EKF_PREC_F64 || p.r_mode == 1 || p.d.kmax != 16) return hipErrorInvalidValue;
-        const bool half = precision == EKF_PREC_F16, f16x3 = p.bf == 2;
-        if (p.nt == 128) return launch_scan_nt128(p, half, f16x3, st);
-        if (p.nt == 64) return launch_scan_nt64(p, half, f16x3, st);
-        return hipErrorInvalidValue;
-    }
-    const dim3 grid(p.G * p.E), block(SCAN_BLOCK);
-    if (p.dbg) {   // phase timers (EKF_OPT_SCAN_STAMPS): the instrumented instantiation
-        if (precision == EKF_PREC_F64) hipLaunchKernelGGL((scan_kernel<double, true, 0>), grid, block, 0, st, p);
-        else if (precision == EKF_PREC_F16) hipLaunchKernelGGL((scan_kernel<_Float16, true, 0>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_kernel<float, true, 0>), grid, block, 0, st, p);
-    } else if (precision != EKF_PREC_F64 && p.r_mode != 1 && p.d.kmax == 16 && p.bf == 2) {
-        if (precision == EKF_PREC_F16) hipLaunchKernelGGL((scan_kernel<_Float16, false, 2>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_kernel<float, false, 2>), grid, block, 0, st, p);
-    } else if (precision != EKF_PREC_F64 && p.r_mode != 1 && p.d.kmax == 16) {
-        if (precision == EKF_PREC_F16) hipLaunchKernelGGL((scan_kernel<_Float16, false, 1>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_kernel<float, false, 1>), grid, block, 0, st, p);
-    } else {
-        if (precision == EKF_PREC_F64) hipLaunchKernelGGL((scan_kernel<double, false, 0>), grid, block, 0, st, p);
-        else if (precision == EKF_PREC_F16) hipLaunchKernelGGL((scan_kernel<_Float16, false, 0>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_kernel<float, false, 0>), grid, block, 0, st, p);
-    }
-    return hipGetLastError();
-}
-
-#endif
-
-// The flush launchers. flush_plan (ekf_flush_plan.h) decides the kernel: launch_downdate switches on the
-// plan, each launcher turns its step count into the template argument. The split-arithmetic launchers
-// are one compilation unit each (EKF_TU 4-6, 9: their instantiations are most of the device code).
-static_assert(PERSIST_MAXS == PST_MAXC, "flush_plan's bound of flush_f32_persist2_kernel");
-
-// One flush launch, timed by the dispatch packet itself when ev_a / ev_b are given
-struct FlushLaunch {
-    const DowndateParams& p;
-    unsigned grid;
-    hipStream_t st;
-    hipEvent_t ev_a, ev_b;
-    template <typename K>
-    void operator()(K kernel, unsigned block = DD_THREADS) const
-    {
-        hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, ev_a, ev_b, 0, p);
-    }
-};
-
-// f(std::integral_constant<int, NS>) for the NS of LO, LO + STEP, ..., HI that equals nsteps, or an error.
-// Counts down: the innermost instantiation is emitted first, so a unit's kernels stay in ascending order
-template <int LO, int HI, int STEP, typename F>
-static hipError_t with_steps(int nsteps, F&& f)
-{
-    static_assert(HI < LO || (HI - LO) % STEP == 0, "HI is one of the steps");
-    if constexpr (HI < LO) {
-        return hipErrorInvalidValue;
-    } else {
-        if (nsteps != HI) return with_steps<LO, HI - STEP, STEP>(nsteps, f);
-        f(std::integral_constant<int, HI>{});
-        return hipGetLastError();
-    }
-}
-
-hipError_t launch_flush_bf24(const FlushLaunch& go, bool half, bool f16);
-hipError_t launch_flush_f16x3(const FlushLaunch& go, bool half);
-hipError_t launch_flush_bf16x6(const FlushLaunch& go, bool half);
-hipError_t launch_flush_f16q(const FlushLaunch& go, bool half);
-
-#if !defined(EKF_TU) || EKF_TU == 9
-hipError_t launch_flush_f16q(const FlushLaunch& go, bool half)
-{
-    return with_steps<QUAD_MINS, F16X3_MAXS, 2>(go.p.nsteps, [&](auto ns) {
-        constexpr int NS = decltype(ns)::value;
-        go(half ? flush_f16q_kernel<_Float16, NS> : flush_f16q_kernel<float, NS>, 64 * Q_WAVES);
-    });
-}
-#endif
-
-#if !defined(EKF_TU) || EKF_TU == 4
-hipError_t launch_flush_f16x3(const FlushLaunch& go, bool half)
-{
-    return with_steps<2, F16X3_MAXS, 2>(go.p.nsteps, [&](auto ns) {
-        constexpr int NS = decltype(ns)::value;
-        go(half ? flush_f32_wave_kernel<_Float16, NS, true, true> : flush_f32_wave_kernel<float, NS, true, true>);
-    });
-}
-#endif
-
-#if !defined(EKF_TU) || EKF_TU == 5
-// the 2 × 4 wave-tile forms (EKF_OPT_FLUSH_FORM = 24): split-bf16 (measured 7 % slower than the
-// 2 × 2 form at T = 12; kept as an option, bit-identical) and split-fp16
-hipError_t launch_flush_bf24(const FlushLaunch& go, bool half, bool f16)
-{
-    if (!f16)
-        return with_steps<2, BF16X6_MAXS, 2>(go.p.nsteps, [&](auto ns) {
-            constexpr int NS = decltype(ns)::value;
-            go(half ? flush_bf24_kernel<_Float16, NS> : flush_bf24_kernel<float, NS>);
-        });
-    return with_steps<2, F16X3_MAXS, 2>(go.p.nsteps, [&](auto ns) {
-        constexpr int NS = decltype(ns)::value;
-        go(half ? flush_bf24_kernel<_Float16, NS, true> : flush_bf24_kernel<float, NS, true>);
-    });
-}
-#endif
-
-#if !defined(EKF_TU) || EKF_TU == 6
-hipError_t launch_flush_bf16x6(const FlushLaunch& go, bool half)
-{
-    return with_steps<2, BF16X6_MAXS, 2>(go.p.nsteps, [&](auto ns) {
-        constexpr int NS = decltype(ns)::value;
-        go(half ? flush_f32_wave_kernel<_Float16, NS, true> : flush_f32_wave_kernel<float, NS, true>);
-    });
-}
-#endif
-
-#if !defined(EKF_TU) || EKF_TU == 2
-hipError_t launch_downdate(const DowndateParams& p, const FlushPlan& plan, int grid, hipStream_t st, hipEvent_t ev_a,
-                           hipEvent_t ev_b)
-{
-    if (p.nsteps != plan.nsteps) return hipErrorInvalidValue;
-    const bool half = plan.storage == EKF_PREC_F16;
-    const FlushLaunch go{p, flush_grid_size(plan.grid, p.ncu, grid, p.E, p.d.nb), st, ev_a, ev_b};
-    switch (plan.family) {
-    case FLUSH_F64_WAVE:
-        return with_steps<1, F64_WAVE_MAXS, 1>(p.nsteps, [&](auto ns) { go(flush_f64_wave_kernel<decltype(ns)::value>); });
-    case FLUSH_F64_TILE: go(downdate_f64_kernel); break;
-    case FLUSH_BF16_2X4: return launch_flush_bf24(go, half, false);
-    case FLUSH_F16_2X4: return launch_flush_bf24(go, half, true);
-    case FLUSH_F16_QUAD: return launch_flush_f16q(go, half);
-    case FLUSH_F16_WAVE: return launch_flush_f16x3(go, half);
-    case FLUSH_BF16_WAVE: return launch_flush_bf16x6(go, half);
-    case FLUSH_F32_WAVE:
-        return with_steps<2, F32_WAVE_MAXS, 2>(p.nsteps, [&](auto ns) {
-            constexpr int NS = decltype(ns)::value;
-            go(half ? flush_f32_wave_kernel<_Float16, NS> : flush_f32_wave_kernel<float, NS>);
-        });
-    case FLUSH_F32_PERSIST: go(half ? flush_f32_persist2_kernel<_Float16> : flush_f32_persist2_kernel<float>); break;
-    case FLUSH_F32_SUPERTILE: go(half ? flush_f32_sb_kernel<_Float16> : flush_f32_sb_kernel<float>); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-#endif
-
-#if !defined(EKF_TU) || EKF_TU == 3
-static int grid_for(int64_t work, int block)
-{
-    int64_t g = (work + block - 1) / block;
-    if (g > 8192) g = 8192;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
-hipError_t launch_pack(const Dims& d, int precision, const double* Pfull, void* Pll, double* Rs,
-                       const int2* tile_rc, int ex, hipStream_t st, int64_t t0, int64_t t1)
-{
-    if (t1 < 0) t1 = d.ntiles;
-    const int grid = grid_for((t1 - t0) * TILE_ELEMS, 256);
-    if (precision == EKF_PREC_F64)
-        hipLaunchKernelGGL(pack_kernel<double>, dim3(grid), dim3(256), 0, st, d, Pfull,
-                           (double*)Pll, Rs, tile_rc, ex, t0, t1);
-    else if (precision == EKF_PREC_F16)
-        hipLaunchKernelGGL(pack_kernel<_Float16>, dim3(grid), dim3(256), 0, st, d, Pfull,
-                           (_Float16*)Pll, Rs, tile_rc, ex, t0, t1);
-    else
-        hipLaunchKernelGGL(pack_kernel<float>, dim3(grid), dim3(256), 0, st, d, Pfull,
-                           (float*)Pll, Rs, tile_rc, ex, t0, t1);
-    return hipGetLastError();
-}
-
-hipError_t launch_unpack(const Dims& d, int precision, double* Pfull, const void* Pll,
-                         const double* Rs, int ex, hipStream_t st, int64_t t0, int64_t t1)
-{
-    if (t1 < 0) t1 = d.ntiles;
-    const int grid = grid_for((int64_t)d.n * d.n, 256);
-    if (precision == EKF_PREC_F64)
-        hipLaunchKernelGGL(unpack_kernel<double>, dim3(grid), dim3(256), 0, st, d, Pfull,
-                           (const double*)Pll, Rs, ex, t0, t1);
-    else if (precision == EKF_PREC_F16)
-        hipLaunchKernelGGL(unpack_kernel<_Float16>, dim3(grid), dim3(256), 0, st, d, Pfull,
-                           (const _Float16*)Pll, Rs, ex, t0, t1);
-    else
-        hipLaunchKernelGGL(unpack_kernel<float>, dim3(grid), dim3(256), 0, st, d, Pfull,
-                           (const float*)Pll, Rs, ex, t0, t1);
-    return hipGetLastError();
-}
-
-hipError_t launch_lowrank(const Dims& d, int precision, const double* diag, const double* U,
-                          int rank, void* Pll, double* Rs, const int2* tile_rc, int ex, hipStream_t st,
-                          int64_t t0, int64_t t1)
-{
-    if (t1 < 0) t1 = d.ntiles;
-    const int grid = grid_for((t1 - t0) * TILE_ELEMS, 256);
-    if (precision == EKF_PREC_F64)
-        hipLaunchKernelGGL(lowrank_kernel<double>, dim3(grid), dim3(256), 0, st, d, diag, U,
-                           rank, (double*)Pll, Rs, tile_rc, ex, t0, t1);
-    else if (precision == EKF_PREC_F16)
-        hipLaunchKernelGGL(lowrank_kernel<_Float16>, dim3(grid), dim3(256), 0, st, d, diag, U,
-                           rank, (_Float16*)Pll, Rs, tile_rc, ex, t0, t1);
-    else
-        hipLaunchKernelGGL(lowrank_kernel<float>, dim3(grid), dim3(256), 0, st, d, diag, U,
-                           rank, (float*)Pll, Rs, tile_rc, ex, t0, t1);
-    return hipGetLastError();
-}
-
-#endif
 
 }  // namespace ekf

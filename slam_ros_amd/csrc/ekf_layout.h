@@ -114,7 +114,7 @@ EKF_HD int64_t ll_offset<double>(int i, int j, int nb)
     return tile_index(bi, bj, nb) * TILE_ELEMS + tile_off_f64(r, c);
 }
 
-// Downdate operands, per 32-row block rb, in MFMA operand order (see ekf_kernels.hip):
+// Downdate operands, per 32-row block rb, in MFMA operand order (see ekf_flush_common.h):
 //   f32: op[rb][lane][s]        = X[rb*32 + (lane&31)][2s + (lane>>5)]          s < kmax/2
 //   f64: op[rb][lane][h*ks + s] = X[rb*32 + 16h + (lane&15)][4s + (lane>>4)]    s < kmax/4
 EKF_HD int64_t op_index_f32(int row, int k, int kmax)
