@@ -38,7 +38,8 @@ extern "C" {
  *    (EKF_SPECULATE, EKF_SPIN_LOG2, EKF_TEST_DROP_WG, EKF_MFREP, EKF_SCAN_STAMPS,
  *    EKF_DD_BLOCKS_PER_CU, EKF_FLUSH_VARIANT); EKF_ARITH_F16X3; the row shard replaced by a
  *    partitioned instance (ekf_shard_create ... ekf_shard_end: tiles partitioned, O(n) state
- *    replicated). */
+ *    replicated). Added since, with the number unchanged (entry points only): ekf_query_joint,
+ *    ekf_query_marginals, ekf_query_joint_device. */
 #define SLAM_EKF_ABI_VERSION 3
 #define EKF_MAX_LINES 64 /* lines per scan per instance; main.cpp:99 reserves 20 */
 
@@ -289,6 +290,39 @@ int ekf_get_ellipse(ekf_ctx* ctx, int e, float axii[2], float* angle);
  * nonsymmv succeeds and it publishes |Re λ| and an angle from the real parts of the complex
  * eigenvector; that branch of GSL is not restated here, axii and angle are left untouched. */
 int ekf_ellipse_of_block(const double P22[4], float axii[2], float* angle);
+
+/* Covariance blocks of chosen landmarks, read without draining. The reference has no such member (its
+ * P_t0 is a host array, Robot.h:62); these replace reading entries of it.
+ * Values: cov equals P_full[rows][:, rows] of the matrix ekf_download_state would return at that
+ *   point, mean the same entries of y, blocks and cross the corresponding entries of that matrix. The
+ *   pending steps of the flush group are applied on read. With EKF_ARITH_EXACT (every storage
+ *   precision) and on fp64 storage this holds bit for bit. On the split arithmetics the pending steps
+ *   are read by the exact per-element chain, as EKF_OPT_MFMA_REPLAY = 0 does, so the values agree with
+ *   the later flush only to the arithmetic's parity bar; with fp16 storage the one to-storage rounding
+ *   the group's flush applies is applied, so every returned value is a representable stored value.
+ * No drain, no state change: the call writes nothing of the instance's state and enqueues no flush;
+ *   the flush schedule, the step count and the result mirror are untouched. The host forms are
+ *   synchronous: one kernel, one copy, one wait on the context stream. The device form only enqueues.
+ * Indices: duplicates and any order are allowed; a landmark at or past savedLineCount reads as the
+ *   zero rows the state holds.
+ * Errors: the host forms return EKF_ERANGE for e out of range, K < 0, K > N or an index outside
+ *   [0, N), EKF_EINVAL for a NULL context (or a NULL list with K > 0 where one is required); a
+ *   partitioned context (ekf_shard_create) returns EKF_EINVAL, as for ekf_localize. In the device form
+ *   an index outside [0, N) gives NaN in that landmark's rows and columns of cov and its entries of
+ *   mean, and is never dereferenced. K == 0 is valid: the pose block and the pose mean. */
+/* Joint marginal of the pose and K landmarks of instance e, of the committed state (every scan
+ * enqueued so far): rows/columns {0,1,2, 3+2j, 4+2j : j in landmarks}. */
+int ekf_query_joint(ekf_ctx* ctx, int e, const int32_t* landmarks, int K,
+                    double* cov /* (3+2K)^2 row-major, may be NULL */,
+                    double* mean /* 3+2K, may be NULL */);
+/* Per-landmark marginals: blocks[k] = the 2x2 block of landmark k (row-major), cross[k] = the 3x2
+ * robot-landmark block P[0:3, 3+2j:5+2j] (row-major), mean[k] = y[3+2j], y[4+2j]. landmarks NULL =
+ * 0..K-1; any output may be NULL. */
+int ekf_query_marginals(ekf_ctx* ctx, int e, const int32_t* landmarks, int K,
+                        double* blocks /* [K][4] */, double* cross /* [K][6] */, double* mean /* [K][2] */);
+/* The joint query for every instance at once, all buffers in device memory, asynchronous on the
+ * context stream: d_landmarks [E][K], d_cov [E][(3+2K)^2], d_mean [E][3+2K] (either may be NULL). */
+int ekf_query_joint_device(ekf_ctx* ctx, const int32_t* d_landmarks, int K, double* d_cov, double* d_mean);
 
 /* One instance with its landmark block partitioned over ranks, for maps
  * whose packed P should not (or cannot) live on one GPU. No reference member maps to these: they

@@ -13,7 +13,9 @@
 //   pipelined  (pipeline = 1): flush f reads X[in] and writes X[out] = the other buffer while the
 //     next group's scans run on S reading X[in] — the output of flush f-1 — with the steps of
 //     groups f and f+1 pending (< 2T); R = 2T.
-// Any call that reads or replaces the landmark block drains (flushes the partial group, syncs).
+// Any call that reads the whole landmark block or replaces it drains (flushes the partial group,
+// syncs); the covariance queries (ekf_query_*) read chosen blocks as an association kernel would,
+// with the pending steps applied on read, and leave the schedule as it is.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -58,6 +60,13 @@ struct ekf_ctx {
     double* y;                // [2][E][n]    copy cur[e] and writes the other; the lead commits it)
     int* cur;                 // [E] committed copy per instance (device; read back when needed)
     double* dense = nullptr;   // n × n fp64 scratch of upload / download / rescale (allocated on first use, kept)
+    // the host queries' result buffers (ekf_query_joint / ekf_query_marginals), sized to the largest
+    // request so far and kept: device scratch, and pinned host memory the one copy lands in, with the
+    // request's landmark indices behind the results (the kernel reads them through q_host_dev)
+    double* q_dev = nullptr;
+    char* q_host = nullptr;
+    char* q_host_dev = nullptr;
+    size_t q_dev_bytes = 0, q_host_bytes = 0;
     // partitioned instance (ekf_shard_create): rank sh_rank of sh_world stores tile rows [sh_r0, sh_r1);
     // the running scan's replicated state
     int sh_rank = -1, sh_world = 0, sh_r0 = 0, sh_r1 = 0;
@@ -242,7 +251,9 @@ static bool upload_table(ekf_ctx* c, D** dst, const std::vector<V>& table, int* 
 static void free_all(ekf_ctx* c)
 {
     for (void* p : c->dev_mem) (void)hipFree(p);
-    for (void* p : {(void*)c->dbg, (void*)c->dense, (void*)c->sh_xbuf, (void*)c->sh_xcols}) (void)hipFree(p);   // (or null)
+    for (void* p : {(void*)c->dbg, (void*)c->dense, (void*)c->q_dev, (void*)c->sh_xbuf, (void*)c->sh_xcols})
+        (void)hipFree(p);   // (or null)
+    if (c->q_host) (void)hipHostFree(c->q_host);
     for (void* p : c->pinned_mem) (void)hipHostFree(p);
     if (c->h_agree) (void)hipHostFree(c->h_agree);
     if (c->ev_in) (void)hipEventDestroy(c->ev_in);
@@ -1498,6 +1509,164 @@ extern "C" int ekf_get_ellipse(ekf_ctx* c, int e, float axii[2], float* angle)
     if (rc) return -rc;
     const double P22[4] = {P33[0], P33[1], P33[3], P33[4]};
     return gsl_ellipse_2x2(P22, axii, angle);
+}
+
+// ---- covariance queries without a drain (slam_ekf.h ekf_query_*; kernel: unit_query.hip) ----
+// The query kernel takes the view the next association kernel would take in enqueue(): X[base] once
+// the event guarding it has passed, the steps [pend0, nsteps) applied on read, the committed copy
+// of the strip and the mean. It runs on S after every scan enqueued so far and changes nothing of
+// the schedule: no flush, no step, no epoch.
+static int enqueue_query(ekf_ctx* c, ekf::QueryParams& qp)
+{
+    if (c->ev_base) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_base, 0));
+    const int np = (int)(c->nsteps - c->pend0);
+    if (np > ekf::PMAX) return EKF_EINVAL;   // unreachable: T <= 24
+    qp.d = c->d;
+    qp.Etot = c->cfg.instances;
+    qp.usym = usym_of(c);
+    qp.bf = c->pmode;
+    qp.npend = np;
+    qp.Pread = xview(c, c->base);
+    qp.Rs = c->Rs;
+    qp.y = c->y;
+    qp.live = c->cur;
+    qp.pexp = c->pexp;
+    for (int q = 0; q < np; q++) qp.pend[q] = slot_of(c, c->pend0 + q);
+    HIP_TRY(ekf::launch_query(qp, c->cfg.precision, c->stream));
+    // Pipelined schedule: the next flush (a drain's, or the group's) writes X[base] on D, ordered
+    // only after ev_scan, which the last scan recorded before this read was enqueued. ev_scan is
+    // recorded again here, behind the query on S, so that flush also waits for the read.
+    if (c->cfg.pipeline) HIP_TRY(hipEventRecord(c->ev_scan, c->stream));
+    return EKF_OK;
+}
+
+// The host queries' buffers for a request of `bytes` result bytes and K indices
+static int query_buffers(ekf_ctx* c, size_t bytes, int K)
+{
+    if (bytes > c->q_dev_bytes) {
+        if (c->q_dev) (void)hipFree(c->q_dev);
+        c->q_dev = nullptr;
+        c->q_dev_bytes = 0;
+        if (hipMalloc((void**)&c->q_dev, bytes) != hipSuccess) {
+            c->q_dev = nullptr;
+            return EKF_ENOMEM;
+        }
+        c->q_dev_bytes = bytes;
+    }
+    const size_t hb = bytes + sizeof(int32_t) * (size_t)K;
+    if (hb > c->q_host_bytes) {
+        if (c->q_host) (void)hipHostFree(c->q_host);
+        c->q_host = c->q_host_dev = nullptr;
+        c->q_host_bytes = 0;
+        if (hipHostMalloc((void**)&c->q_host, hb) != hipSuccess) {
+            c->q_host = nullptr;
+            return EKF_ENOMEM;
+        }
+        if (hipHostGetDevicePointer((void**)&c->q_host_dev, c->q_host, 0) != hipSuccess) {
+            (void)hipHostFree(c->q_host);
+            c->q_host = c->q_host_dev = nullptr;
+            return EKF_EDEVICE;
+        }
+        c->q_host_bytes = hb;
+    }
+    return EKF_OK;
+}
+
+// Argument checks shared by the host forms (before any HIP call)
+static int query_check(const ekf_ctx* c, int e, const int32_t* landmarks, int K, bool need_list)
+{
+    if (!c || c->sh_world > 0) return EKF_EINVAL;
+    if (e < 0 || e >= c->cfg.instances || K < 0 || K > c->d.N) return EKF_ERANGE;
+    if (need_list && K > 0 && !landmarks) return EKF_EINVAL;
+    if (landmarks)
+        for (int k = 0; k < K; k++)
+            if (landmarks[k] < 0 || landmarks[k] >= c->d.N) return EKF_ERANGE;
+    return EKF_OK;
+}
+
+// One kernel, one copy (into the pinned buffer), one wait; the results then leave by memcpy
+// (after query_buffers for this request)
+static int run_host_query(ekf_ctx* c, ekf::QueryParams& qp, const int32_t* landmarks, size_t bytes)
+{
+    if (landmarks) {
+        memcpy(c->q_host + bytes, landmarks, sizeof(int32_t) * (size_t)qp.K);
+        qp.landmarks = reinterpret_cast<const int32_t*>(c->q_host_dev + bytes);
+    }
+    const int rc = enqueue_query(c, qp);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->q_host, c->q_dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return EKF_OK;
+}
+
+extern "C" int ekf_query_joint(ekf_ctx* c, int e, const int32_t* landmarks, int K, double* cov, double* mean)
+{
+    int rc = query_check(c, e, landmarks, K, true);
+    if (rc) return rc;
+    if (!cov && !mean) return EKF_OK;
+    const size_t nq = 3 + 2 * (size_t)K;
+    const size_t ncov = cov ? nq * nq : 0;
+    ekf::QueryParams qp;
+    memset(&qp, 0, sizeof(qp));
+    qp.mode = ekf::QUERY_JOINT;
+    qp.E = 1;
+    qp.e0 = e;
+    qp.K = K;
+    rc = query_buffers(c, sizeof(double) * (ncov + nq), K);
+    if (rc) return rc;
+    qp.cov = cov ? c->q_dev : nullptr;
+    qp.mean = c->q_dev + ncov;
+    rc = run_host_query(c, qp, landmarks, sizeof(double) * (ncov + nq));
+    if (rc) return rc;
+    const double* h = reinterpret_cast<const double*>(c->q_host);
+    if (cov) memcpy(cov, h, sizeof(double) * ncov);
+    if (mean) memcpy(mean, h + ncov, sizeof(double) * nq);
+    return EKF_OK;
+}
+
+extern "C" int ekf_query_marginals(ekf_ctx* c, int e, const int32_t* landmarks, int K, double* blocks,
+                                   double* cross, double* mean)
+{
+    int rc = query_check(c, e, landmarks, K, false);
+    if (rc) return rc;
+    if (K == 0 || (!blocks && !cross && !mean)) return EKF_OK;
+    const size_t k = (size_t)K;
+    ekf::QueryParams qp;
+    memset(&qp, 0, sizeof(qp));
+    qp.mode = ekf::QUERY_MARGINALS;
+    qp.E = 1;
+    qp.e0 = e;
+    qp.K = K;
+    rc = query_buffers(c, sizeof(double) * 12 * k, landmarks ? K : 0);
+    if (rc) return rc;
+    qp.blocks = c->q_dev;
+    qp.cross = c->q_dev + 4 * k;
+    qp.mean = c->q_dev + 10 * k;
+    rc = run_host_query(c, qp, landmarks, sizeof(double) * 12 * k);
+    if (rc) return rc;
+    const double* h = reinterpret_cast<const double*>(c->q_host);
+    if (blocks) memcpy(blocks, h, sizeof(double) * 4 * k);
+    if (cross) memcpy(cross, h + 4 * k, sizeof(double) * 6 * k);
+    if (mean) memcpy(mean, h + 10 * k, sizeof(double) * 2 * k);
+    return EKF_OK;
+}
+
+extern "C" int ekf_query_joint_device(ekf_ctx* c, const int32_t* d_landmarks, int K, double* d_cov, double* d_mean)
+{
+    if (!c || c->sh_world > 0) return EKF_EINVAL;
+    if (K < 0 || K > c->d.N) return EKF_ERANGE;
+    if (K > 0 && !d_landmarks) return EKF_EINVAL;
+    if (!d_cov && !d_mean) return EKF_OK;
+    ekf::QueryParams qp;
+    memset(&qp, 0, sizeof(qp));
+    qp.mode = ekf::QUERY_JOINT;
+    qp.E = c->cfg.instances;
+    qp.e0 = 0;
+    qp.K = K;
+    qp.landmarks = K > 0 ? d_landmarks : nullptr;
+    qp.cov = d_cov;
+    qp.mean = d_mean;
+    return enqueue_query(c, qp);
 }
 
 extern "C" size_t ekf_landmark_block_bytes(const ekf_ctx* c)

@@ -26,7 +26,8 @@
 // the flush will store (tests/test_gpu_parity.py::test_deferred_flush_equals_drained).
 //
 // The device code by topic: ekf_kernels.hip (the association: its arithmetic, the exchange, scan_kernel,
-// the partitioned instance), ekf_flush_common.h and one ekf_flush_*.h per flush family, ekf_pack.h.
+// the partitioned instance), ekf_flush_common.h and one ekf_flush_*.h per flush family, ekf_pack.h;
+// unit_query.hip holds the covariance queries' kernel (pll_block on chosen landmarks).
 // Each unit_*.hip includes what its launchers instantiate (build.py: UNITS).
 #pragma once
 

@@ -248,6 +248,39 @@ struct DowndateParams {
     Slot steps[PMAX];
 };
 
+// Covariance blocks of chosen landmarks, read as the next association kernel would read them: the
+// landmark block Pread with the pending steps applied on read (pll_block), the robot strip and the
+// mean from the committed copy live[e]. Nothing of the state is written (unit_query.hip).
+//   QUERY_JOINT      cov [E][(3+2K)²] rows / columns {0, 1, 2, 3+2j, 4+2j : j in landmarks}, mean [E][3+2K]
+//   QUERY_MARGINALS  blocks [E][K][4], cross [E][K][6] = P[0:3, 3+2j : 5+2j], mean [E][K][2]
+// An index outside [0, N) is never dereferenced: its entries are NaN.
+enum { QUERY_JOINT = 0, QUERY_MARGINALS = 1 };
+constexpr int QUERY_THREADS = 256;   // joint: four waves, one row landmark each, 64 column landmarks wide
+constexpr int QUERY_ROWS = QUERY_THREADS / 64;
+struct QueryParams {
+    Dims d;
+    int mode;
+    int E;                // instances in this launch (grid.y): outputs and index lists are per launch row
+    int e0;               // first instance of this launch
+    int Etot;             // instances of the context
+    int K;                // landmarks queried per instance
+    int usym;             // symmetric fp32 operands (ScanParams::usym)
+    int bf;               // split-plane context: fp16 storage rounded once, after the pending steps
+    int npend;            // steps not yet in Pread, applied on read (in order)
+    const void* Pread;    // [Etot][ntiles][1024]
+    const double* Rs;     // [2][Etot][3][n]
+    const double* y;      // [2][Etot][n]
+    const int* live;      // [Etot]
+    const int* pexp;      // [Etot]
+    const int32_t* landmarks;   // [E][K] (device-readable; nullptr: 0 .. K − 1)
+    double* cov;          // QUERY_JOINT (nullptr: the mean only)
+    double* mean;
+    double* blocks;       // QUERY_MARGINALS
+    double* cross;
+    Slot pend[PMAX];      // pending steps, oldest first
+};
+hipError_t launch_query(const QueryParams& p, int precision, hipStream_t st);
+
 hipError_t launch_scan(const ScanParams& p, int precision, hipStream_t st);
 int scan_blocks_per_cu(int precision);
 size_t scan_lds_bytes(int precision);   // static LDS of the association kernel

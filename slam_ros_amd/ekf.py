@@ -42,6 +42,7 @@ EXPORTED = [
     "ekf_set_stream", "ekf_sync", "ekf_set_option", "ekf_get_option", "ekf_reset_instance", "ekf_localize", "ekf_localize_device",
     "ekf_predict", "ekf_update", "ekf_read_results", "ekf_upload_state", "ekf_download_state",
     "ekf_init_lowrank", "ekf_storage_exponent", "ekf_rescale", "ekf_get_pose_cov", "ekf_get_ellipse", "ekf_ellipse_of_block",
+    "ekf_query_joint", "ekf_query_marginals", "ekf_query_joint_device",
     "ekf_landmark_block_bytes",
     "ekf_state_dim", "ekf_profile_enable", "ekf_profile_read", "ekf_profile_flushes",
     "ekf_flush_kernel_name", "ekf_debug_scan_stamps", "ekf_debug_result_words",
@@ -127,6 +128,9 @@ def load_library(path: str = ""):
                                            ctypes.POINTER(ctypes.c_float)]),
         "ekf_ellipse_of_block": (ctypes.c_int, [dp, ctypes.POINTER(ctypes.c_float),
                                                 ctypes.POINTER(ctypes.c_float)]),
+        "ekf_query_joint": (ctypes.c_int, [vp, ctypes.c_int, ip, ctypes.c_int, dp, dp]),
+        "ekf_query_marginals": (ctypes.c_int, [vp, ctypes.c_int, ip, ctypes.c_int, dp, dp, dp]),
+        "ekf_query_joint_device": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp]),
         "ekf_landmark_block_bytes": (sz, [vp]),
         "ekf_state_dim": (ctypes.c_int, [vp]),
         "ekf_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
@@ -344,6 +348,41 @@ class Ensemble:
         _check(self._lib.ekf_get_pose_cov(self._h, e, _dp(out)), "ekf_get_pose_cov")
         return out.reshape(3, 3)
 
+    def query_joint(self, e: int, landmarks):
+        """Joint marginal of the pose and the given landmarks of instance e, read without draining
+        (slam_ekf.h ekf_query_joint): (cov, mean) = (P[rows][:, rows], y[rows]) for rows
+        {0, 1, 2, 3 + 2j, 4 + 2j : j in landmarks}; duplicates and any order are allowed."""
+        lm = np.ascontiguousarray(np.asarray(landmarks, dtype=np.int32).reshape(-1))
+        K = int(lm.size)
+        cov = np.zeros((3 + 2 * K, 3 + 2 * K))
+        mean = np.zeros(3 + 2 * K)
+        _check(self._lib.ekf_query_joint(self._h, e, lm.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), K,
+                                         _dp(cov), _dp(mean)), "ekf_query_joint")
+        return cov, mean
+
+    def query_marginals(self, e: int, landmarks=None, count=None):
+        """Per-landmark marginals of instance e, read without draining (ekf_query_marginals):
+        (blocks [K, 2, 2], cross [K, 3, 2] = P[0:3, 3 + 2j : 5 + 2j], mean [K, 2]). landmarks None:
+        the first `count` landmarks (default: all of the capacity)."""
+        if landmarks is None:
+            lm, K = None, self.capacity if count is None else int(count)
+        else:
+            lm = np.ascontiguousarray(np.asarray(landmarks, dtype=np.int32).reshape(-1))
+            K = int(lm.size) if count is None else int(count)
+        blocks, cross, mean = np.zeros((K, 2, 2)), np.zeros((K, 3, 2)), np.zeros((K, 2))
+        lp = None if lm is None else lm.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        _check(self._lib.ekf_query_marginals(self._h, e, lp, K, _dp(blocks), _dp(cross), _dp(mean)),
+               "ekf_query_marginals")
+        return blocks, cross, mean
+
+    def query_joint_device(self, d_landmarks: int, K: int, d_cov: int, d_mean: int):
+        """The joint query of every instance, buffers in device memory (raw pointers: landmarks
+        [E, K] int32, cov [E, (3 + 2K)²], mean [E, 3 + 2K]; either output may be 0); asynchronous on
+        the context stream."""
+        _check(self._lib.ekf_query_joint_device(self._h, ctypes.c_void_p(d_landmarks or None), int(K),
+                                                ctypes.c_void_p(d_cov or None), ctypes.c_void_p(d_mean or None)),
+               "ekf_query_joint_device")
+
     def ellipse(self, e: int = 0):
         axii = (ctypes.c_float * 2)()
         ang = ctypes.c_float()
@@ -466,6 +505,12 @@ class Robot:
     def getEllipse(self):
         ok, axii, angle = self._ens.ellipse(0)
         return ok, axii, angle
+
+    def landmarkEllipse(self, j: int):
+        """getEllipse's arithmetic (Robot.cpp:73-124) on landmark j's 2x2 block, read without
+        draining the flush (the reference has no such member): (ok, axii, angle)."""
+        blocks, _, _ = self._ens.query_marginals(0, [int(j)])
+        return ellipse_of_block(blocks[0])
 
     @property
     def P_t0(self) -> np.ndarray:

@@ -128,6 +128,17 @@ public:
         return ekf_get_ellipse(ctx_, 0, axii, &angle) == 1;
     }
 
+    // The same ellipse for landmark j's 2x2 block (the reference has no such member): the block is
+    // read on the device with the pending downdates applied (ekf_query_marginals), so the deferred
+    // flush is not drained and nothing of P_t0 is downloaded
+    bool landmarkEllipse(int j, float axii[2], float* angle)
+    {
+        const int32_t lm = (int32_t)j;
+        double blk[4];
+        if (!angle || ekf_query_marginals(ctx_, 0, &lm, 1, blk, nullptr, nullptr) != EKF_OK) return false;
+        return ekf_ellipse_of_block(blk, axii, angle) == 1;
+    }
+
     void normalizeRadian(double& rad) { normalize_radian(rad); }
 
     void setMirror(Mirror m)
