@@ -39,7 +39,7 @@ extern "C" {
  *    EKF_DD_BLOCKS_PER_CU, EKF_FLUSH_VARIANT); EKF_ARITH_F16X3; the row shard replaced by a
  *    partitioned instance (ekf_shard_create ... ekf_shard_end: tiles partitioned, O(n) state
  *    replicated). Added since, with the number unchanged (entry points only): ekf_query_joint,
- *    ekf_query_marginals, ekf_query_joint_device. */
+ *    ekf_query_marginals, ekf_query_joint_device; ekf_gate_lines, ekf_gate_lines_device. */
 #define SLAM_EKF_ABI_VERSION 3
 #define EKF_MAX_LINES 64 /* lines per scan per instance; main.cpp:99 reserves 20 */
 
@@ -323,6 +323,54 @@ int ekf_query_marginals(ekf_ctx* ctx, int e, const int32_t* landmarks, int K,
 /* The joint query for every instance at once, all buffers in device memory, asynchronous on the
  * context stream: d_landmarks [E][K], d_cov [E][(3+2K)^2], d_mean [E][3+2K] (either may be NULL). */
 int ekf_query_joint_device(ekf_ctx* ctx, const int32_t* d_landmarks, int K, double* d_cov, double* d_mean);
+
+/* Trial lines scored against the map, state untouched: which landmark the association would pick for
+ * a line, how far away it is, and whether there was a second candidate. The reference has no such
+ * member: its association (Robot.cpp:313-498) is first-fit inside localize, which commits the scan.
+ * Independent lines: each line is evaluated on its own against every saved landmark j <
+ *   savedLineCount, as the first line of a scan: no sequential update between the lines and no
+ *   "already matched" skip. R is what the association builds for index i in the list under the
+ *   context's r_mode (EKF_R_AS_WRITTEN: it follows the line's index). d2[i][j] is +inf for
+ *   j >= savedLineCount. The gate is the association's own expression, so a NaN distance passes.
+ * Pose and P, enc given: the call predicts on read. x_pre, the motion Jacobian and the predicted
+ *   3x3 block come from the committed pose exactly as ekf_predict computes them (Robot.cpp:130-286),
+ *   and each candidate's robot-landmark columns are predicted likewise; nothing is written.
+ *   hits[0].first is therefore the match ekf_localize(enc, lines) would report for line 0.
+ * Pose and P, enc == NULL: between ekf_predict and ekf_update the call uses the inputs ekf_update
+ *   would use now (the committed, predicted strip and x_pre); otherwise the committed pose and strip
+ *   with no motion. Between ekf_predict and ekf_update a call with enc != NULL returns EKF_EINVAL
+ *   (the strip is already predicted); the state is "predicted" from ekf_predict until the next
+ *   update, localize or state write (reset, upload, ekf_init_lowrank, ekf_rescale).
+ * Landmark blocks: read as the covariance queries read them, the pending steps of the flush group
+ *   applied on read and, with fp16 storage on the split arithmetics, the group's one to-storage
+ *   rounding. With EKF_ARITH_EXACT (every storage precision) and on fp64 storage this is the
+ *   association's own view, bit for bit. On the split arithmetics the pending steps are read by the
+ *   exact per-element chain, as for the queries, so the distances agree with the association's to the
+ *   arithmetic's parity bar.
+ * No drain, no state change: the call writes nothing of the instance's state and enqueues no flush;
+ *   the flush schedule, the step count and the result mirror are untouched. The host form is
+ *   synchronous: two kernels, one copy, one wait on the context stream. The device form only
+ *   enqueues; it writes the entries i >= nlines[e] of d_hits as first = nearest = -1, npass = 0.
+ * Errors: EKF_ERANGE for e out of range or L outside [0, max_lines]; EKF_EINVAL for a NULL context,
+ *   NULL lines with L > 0, NULL hits, or a partitioned context (ekf_shard_create). L == 0 is valid. */
+typedef struct ekf_gate_hit {
+    int32_t first;     /* lowest landmark index whose distance passes the gate (what Robot.cpp:313-498
+                          picks for this line when no earlier line of the scan matched); -1: none */
+    int32_t nearest;   /* argmin |d2| over the candidates (lowest index on ties, NaN ignored); -1: none */
+    int32_t npass;     /* candidates that pass the gate */
+    int32_t status;    /* EKF_ST_SINGULAR_S / EKF_ST_PRECISION (its gate half, at the storage precision
+                          of the gate) over the candidates the reference would evaluate: 0..first, or
+                          all when first == -1 */
+    double d2_first, d2_nearest;   /* vT S^-1 v as the reference computes it (Robot.cpp:479-486); NaN if none */
+    double S[4], v[2];             /* innovation covariance and innovation of `first`, or of `nearest`
+                                      when nothing passes; zeros when there is no candidate */
+} ekf_gate_hit;
+int ekf_gate_lines(ekf_ctx* ctx, int e, const double enc[3] /* may be NULL */, const ekf_line* lines, int L,
+                   ekf_gate_hit* hits /* [L] */, double* d2 /* [L][N], may be NULL */);
+/* Every instance at once, all buffers in device memory, asynchronous on the context stream. */
+int ekf_gate_lines_device(ekf_ctx* ctx, const double* d_enc /* [E][3] or NULL */,
+                          const ekf_line* d_lines /* [E][max_lines] */, const int32_t* d_nlines /* [E] */,
+                          ekf_gate_hit* d_hits /* [E][max_lines] */, double* d_d2 /* [E][max_lines][N] or NULL */);
 
 /* One instance with its landmark block partitioned over ranks, for maps
  * whose packed P should not (or cannot) live on one GPU. No reference member maps to these: they

@@ -14,8 +14,9 @@
 //     next group's scans run on S reading X[in] — the output of flush f-1 — with the steps of
 //     groups f and f+1 pending (< 2T); R = 2T.
 // Any call that reads the whole landmark block or replaces it drains (flushes the partial group,
-// syncs); the covariance queries (ekf_query_*) read chosen blocks as an association kernel would,
-// with the pending steps applied on read, and leave the schedule as it is.
+// syncs); the covariance queries (ekf_query_*) and the gate query (ekf_gate_lines*) read chosen
+// blocks as an association kernel would, with the pending steps applied on read, and leave the
+// schedule as it is.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -67,6 +68,12 @@ struct ekf_ctx {
     char* q_host = nullptr;
     char* q_host_dev = nullptr;
     size_t q_dev_bytes = 0, q_host_bytes = 0;
+    // ekf_gate_lines: the candidates' flag bytes [E][max_lines][N] and the waves' partial records
+    // [E][max_lines][⌈N/64⌉] (listed context memory, made on first use); predicted: ekf_predict ran and
+    // no update, localize or state write since (the committed strip is the predicted one)
+    unsigned char* g_flags = nullptr;
+    ekf::GatePart* g_part = nullptr;
+    int predicted = 0;
     // partitioned instance (ekf_shard_create): rank sh_rank of sh_world stores tile rows [sh_r0, sh_r1);
     // the running scan's replicated state
     int sh_rank = -1, sh_world = 0, sh_r0 = 0, sh_r1 = 0;
@@ -292,6 +299,7 @@ static int drain(ekf_ctx* c)
 static int begin_state_write(ekf_ctx* c)
 {
     c->mirror_epoch = 0;
+    c->predicted = 0;
     return drain(c);
 }
 
@@ -967,8 +975,10 @@ static int enqueue(ekf_ctx* c, int phase, const double* enc, const ekf_line* lin
         EvPair* pr = prof_begin(c, 0, c->stream);
         HIP_TRY(launch_scans(c, sp));
         prof_end(c, pr, c->stream);
+        c->predicted = 1;
         return EKF_OK;
     }
+    c->predicted = 0;
     // X[base] and the ring slot this step reuses are released by the event guarding base
     if (c->ev_base) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_base, 0));
     const int np = (int)(c->nsteps - c->pend0);
@@ -1516,7 +1526,9 @@ extern "C" int ekf_get_ellipse(ekf_ctx* c, int e, float axii[2], float* angle)
 // the event guarding it has passed, the steps [pend0, nsteps) applied on read, the committed copy
 // of the strip and the mean. It runs on S after every scan enqueued so far and changes nothing of
 // the schedule: no flush, no step, no epoch.
-static int enqueue_query(ekf_ctx* c, ekf::QueryParams& qp)
+// (ekf_gate_lines takes the same view: begin_read / end_read are the hazard handling of both.)
+template <typename P>   // QueryParams or GateParams: the view's fields
+static int begin_read(ekf_ctx* c, P& qp)
 {
     if (c->ev_base) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_base, 0));
     const int np = (int)(c->nsteps - c->pend0);
@@ -1532,16 +1544,29 @@ static int enqueue_query(ekf_ctx* c, ekf::QueryParams& qp)
     qp.live = c->cur;
     qp.pexp = c->pexp;
     for (int q = 0; q < np; q++) qp.pend[q] = slot_of(c, c->pend0 + q);
-    HIP_TRY(ekf::launch_query(qp, c->cfg.precision, c->stream));
+    return EKF_OK;
+}
+
+static int end_read(ekf_ctx* c)
+{
     // Pipelined schedule: the next flush (a drain's, or the group's) writes X[base] on D, ordered
     // only after ev_scan, which the last scan recorded before this read was enqueued. ev_scan is
-    // recorded again here, behind the query on S, so that flush also waits for the read.
+    // recorded again here, behind the read on S, so that flush also waits for the read.
     if (c->cfg.pipeline) HIP_TRY(hipEventRecord(c->ev_scan, c->stream));
     return EKF_OK;
 }
 
-// The host queries' buffers for a request of `bytes` result bytes and K indices
-static int query_buffers(ekf_ctx* c, size_t bytes, int K)
+static int enqueue_query(ekf_ctx* c, ekf::QueryParams& qp)
+{
+    const int rc = begin_read(c, qp);
+    if (rc) return rc;
+    HIP_TRY(ekf::launch_query(qp, c->cfg.precision, c->stream));
+    return end_read(c);
+}
+
+// The host forms' buffers for a request of `bytes` result bytes and `tail` bytes of inputs behind them
+// in the pinned buffer (the queries' indices; the gate's lines and encoder pose)
+static int query_buffers(ekf_ctx* c, size_t bytes, size_t tail)
 {
     if (bytes > c->q_dev_bytes) {
         if (c->q_dev) (void)hipFree(c->q_dev);
@@ -1553,7 +1578,7 @@ static int query_buffers(ekf_ctx* c, size_t bytes, int K)
         }
         c->q_dev_bytes = bytes;
     }
-    const size_t hb = bytes + sizeof(int32_t) * (size_t)K;
+    const size_t hb = bytes + tail;
     if (hb > c->q_host_bytes) {
         if (c->q_host) (void)hipHostFree(c->q_host);
         c->q_host = c->q_host_dev = nullptr;
@@ -1612,7 +1637,7 @@ extern "C" int ekf_query_joint(ekf_ctx* c, int e, const int32_t* landmarks, int 
     qp.E = 1;
     qp.e0 = e;
     qp.K = K;
-    rc = query_buffers(c, sizeof(double) * (ncov + nq), K);
+    rc = query_buffers(c, sizeof(double) * (ncov + nq), sizeof(int32_t) * (size_t)K);
     if (rc) return rc;
     qp.cov = cov ? c->q_dev : nullptr;
     qp.mean = c->q_dev + ncov;
@@ -1637,7 +1662,7 @@ extern "C" int ekf_query_marginals(ekf_ctx* c, int e, const int32_t* landmarks, 
     qp.E = 1;
     qp.e0 = e;
     qp.K = K;
-    rc = query_buffers(c, sizeof(double) * 12 * k, landmarks ? K : 0);
+    rc = query_buffers(c, sizeof(double) * 12 * k, landmarks ? sizeof(int32_t) * k : 0);
     if (rc) return rc;
     qp.blocks = c->q_dev;
     qp.cross = c->q_dev + 4 * k;
@@ -1667,6 +1692,90 @@ extern "C" int ekf_query_joint_device(ekf_ctx* c, const int32_t* d_landmarks, in
     qp.cov = d_cov;
     qp.mean = d_mean;
     return enqueue_query(c, qp);
+}
+
+// ---- trial lines gated against the map (slam_ekf.h ekf_gate_lines; kernels: unit_gate.hip) ----
+// The view and the hazard handling of the queries (begin_read / end_read), the committed pose, and
+// two launches on S: nothing of the schedule or the state changes.
+static int enqueue_gate(ekf_ctx* c, ekf::GateParams& gp)
+{
+    const size_t rows = (size_t)c->cfg.instances * c->d.max_lines;
+    const int nw = (c->d.N + 63) / 64;
+    if (!c->g_flags) {
+        void* fl = nullptr;
+        void* pt = nullptr;
+        if (!dev_alloc(c, &fl, rows * c->d.N) || !dev_alloc(c, &pt, rows * nw * sizeof(ekf::GatePart)))
+            return EKF_ENOMEM;   // (listed either way: free_all releases what was made)
+        c->g_flags = (unsigned char*)fl;
+        c->g_part = (ekf::GatePart*)pt;
+    }
+    const int rc = begin_read(c, gp);
+    if (rc) return rc;
+    gp.pose = c->pose;
+    gp.xpre = c->xpre;
+    gp.saved = c->saved;
+    gp.use_xpre = c->predicted;
+    gp.r_mode = c->cfg.r_mode;
+    gp.nw = nw;
+    gp.gate = c->cfg.mahalanobis;
+    gp.enc_noise = c->cfg.encoder_noise;
+    gp.flags = c->g_flags;
+    gp.part = c->g_part;
+    HIP_TRY(ekf::launch_gate(gp, c->cfg.precision, c->stream));
+    return end_read(c);
+}
+
+extern "C" int ekf_gate_lines(ekf_ctx* c, int e, const double enc[3], const ekf_line* lines, int L,
+                              ekf_gate_hit* hits, double* d2)
+{
+    if (!c || c->sh_world > 0) return EKF_EINVAL;
+    if (e < 0 || e >= c->cfg.instances || L < 0 || L > c->d.max_lines) return EKF_ERANGE;
+    if ((L > 0 && !lines) || !hits) return EKF_EINVAL;
+    if (enc && c->predicted) return EKF_EINVAL;   // the committed strip is already the predicted one
+    if (L == 0) return EKF_OK;
+    // device scratch [hits | d2], the pinned buffer [hits | d2 | lines | enc] (inputs behind the results)
+    const size_t nh = sizeof(ekf_gate_hit) * (size_t)L;
+    const size_t nd = d2 ? sizeof(double) * (size_t)L * c->d.N : 0;
+    const size_t nl = sizeof(ekf_line) * (size_t)L;
+    int rc = query_buffers(c, nh + nd, nl + 3 * sizeof(double));
+    if (rc) return rc;
+    memcpy(c->q_host + nh + nd, lines, nl);
+    if (enc) memcpy(c->q_host + nh + nd + nl, enc, 3 * sizeof(double));
+    ekf::GateParams gp;
+    memset(&gp, 0, sizeof(gp));
+    gp.E = 1;
+    gp.e0 = e;
+    gp.L = L;
+    gp.lines = reinterpret_cast<const ekf_line*>(c->q_host_dev + nh + nd);
+    gp.enc = enc ? reinterpret_cast<const double*>(c->q_host_dev + nh + nd + nl) : nullptr;
+    char* dev = reinterpret_cast<char*>(c->q_dev);
+    gp.hits = reinterpret_cast<ekf_gate_hit*>(dev);
+    gp.d2 = d2 ? reinterpret_cast<double*>(dev + nh) : nullptr;
+    rc = enqueue_gate(c, gp);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->q_host, c->q_dev, nh + nd, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memcpy(hits, c->q_host, nh);
+    if (d2) memcpy(d2, c->q_host + nh, nd);
+    return EKF_OK;
+}
+
+extern "C" int ekf_gate_lines_device(ekf_ctx* c, const double* d_enc, const ekf_line* d_lines,
+                                     const int32_t* d_nlines, ekf_gate_hit* d_hits, double* d_d2)
+{
+    if (!c || c->sh_world > 0 || !d_lines || !d_nlines || !d_hits) return EKF_EINVAL;
+    if (d_enc && c->predicted) return EKF_EINVAL;
+    ekf::GateParams gp;
+    memset(&gp, 0, sizeof(gp));
+    gp.E = c->cfg.instances;
+    gp.e0 = 0;
+    gp.L = 0;
+    gp.enc = d_enc;
+    gp.lines = d_lines;
+    gp.nlines = d_nlines;
+    gp.hits = d_hits;
+    gp.d2 = d_d2;
+    return enqueue_gate(c, gp);
 }
 
 extern "C" size_t ekf_landmark_block_bytes(const ekf_ctx* c)

@@ -26,8 +26,10 @@
 // the flush will store (tests/test_gpu_parity.py::test_deferred_flush_equals_drained).
 //
 // The device code by topic: ekf_kernels.hip (the association: its arithmetic, the exchange, scan_kernel,
-// the partitioned instance), ekf_flush_common.h and one ekf_flush_*.h per flush family, ekf_pack.h;
-// unit_query.hip holds the covariance queries' kernel (pll_block on chosen landmarks).
+// the partitioned instance), ekf_gate.h (the gate arithmetic of one candidate, shared with the gate
+// query), ekf_flush_common.h and one ekf_flush_*.h per flush family, ekf_pack.h;
+// unit_query.hip holds the covariance queries' kernel (pll_block on chosen landmarks), unit_gate.hip
+// the gate query's two kernels (trial lines against every saved landmark, state untouched).
 // Each unit_*.hip includes what its launchers instantiate (build.py: UNITS).
 #pragma once
 
@@ -524,6 +526,20 @@ __device__ __forceinline__ void pll_block(const PllView<T>& v, int i0, int j0, d
     double o[1][4];
     pll_blocks<T, 1>(v, i0, js, o);
     out[0] = o[0][0]; out[1] = o[0][1]; out[2] = o[0][2]; out[3] = o[0][3];
+}
+
+// the to-storage rounding a split-plane group's flush applies once (fp16 storage, `once` = a
+// split-plane context; the per-step rounding of the exact arithmetic already happened in pll_block:
+// PllView::rnd): the reads that leave the state untouched (unit_query.hip, unit_gate.hip) apply it
+template <typename T>
+__device__ __forceinline__ void query_round(bool once, int ex, double (&o)[4])
+{
+    if constexpr (Stor<T>::half) {
+        if (once) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) o[k] = from_domain<T>(round_step<T>(to_domain<T>(o[k], ex)), ex);
+        }
+    }
 }
 
 }  // namespace ekf

@@ -281,6 +281,52 @@ struct QueryParams {
 };
 hipError_t launch_query(const QueryParams& p, int precision, hipStream_t st);
 
+// Trial lines gated against every saved landmark (unit_gate.hip), each as the first line of a scan;
+// the same read-only view as QueryParams (its first fields, filled by the same preamble), plus the
+// committed pose. Lines, hit records and distances are per launch row (instance e0 + row), max_lines
+// apart; flags and part are the context's scratch.
+constexpr int GATE_THREADS = 256;   // pass 1: landmarks per workgroup, one partial record per wave
+enum { GATE_FL_SINGULAR = 1, GATE_FL_AMB = 2 };   // per-candidate flag byte
+struct GatePart {      // one wave's 64 landmarks against one line
+    int first;         // lowest passing landmark, −1: none
+    int nearest;       // landmark at the smallest finite |d2| (lowest on ties), −1: none
+    int npass;
+    int pad;
+    double cf[7];      // d2, S[4], v[2] of first
+    double cn[7];      // ... of nearest
+};
+struct GateParams {
+    Dims d;
+    int E;                // instances in this launch (grid.y)
+    int e0;               // first instance of this launch
+    int Etot;             // instances of the context
+    int usym;             // symmetric fp32 operands (ScanParams::usym)
+    int bf;               // split-plane context: fp16 storage rounded once, after the pending steps
+    int npend;            // steps not yet in Pread, applied on read (in order)
+    const void* Pread;    // [Etot][ntiles][1024]
+    const double* Rs;     // [2][Etot][3][n]
+    const double* y;      // [2][Etot][n]
+    const int* live;      // [Etot]
+    const int* pexp;      // [Etot]
+    const double* pose;   // [Etot][3] committed pose
+    const double* xpre;   // [Etot][3] x_pre of the last ekf_predict
+    const int* saved;     // [Etot]
+    int use_xpre;         // enc == nullptr: 1 between ekf_predict and ekf_update (x_pre), 0 the pose
+    int r_mode;
+    int L;                // lines of every row (nlines == nullptr: the host form)
+    int nw;               // partial records per line: ⌈N / 64⌉
+    double gate, enc_noise;
+    const double* enc;    // [E][3] (per launch row) the predict is applied on read; nullptr: no motion
+    const ekf_line* lines;// [E][max_lines]
+    const int* nlines;    // [E] (the device form: unused hit entries are written as empty); or nullptr
+    ekf_gate_hit* hits;   // [E][max_lines]
+    double* d2;           // [E][max_lines][N] or nullptr
+    unsigned char* flags; // [E][max_lines][N]
+    GatePart* part;       // [E][max_lines][nw]
+    Slot pend[PMAX];      // pending steps, oldest first
+};
+hipError_t launch_gate(const GateParams& p, int precision, hipStream_t st);
+
 hipError_t launch_scan(const ScanParams& p, int precision, hipStream_t st);
 int scan_blocks_per_cu(int precision);
 size_t scan_lds_bytes(int precision);   // static LDS of the association kernel

@@ -12,19 +12,6 @@
 
 namespace ekf {
 
-// the to-storage rounding a split-plane group's flush applies once (fp16 storage; the per-step
-// rounding of the exact arithmetic already happened in pll_block: PllView::rnd)
-template <typename T>
-__device__ __forceinline__ void query_round(const QueryParams& p, int ex, double (&o)[4])
-{
-    if constexpr (Stor<T>::half) {
-        if (p.bf) {
-#pragma unroll
-            for (int k = 0; k < 4; k++) o[k] = from_domain<T>(round_step<T>(to_domain<T>(o[k], ex)), ex);
-        }
-    }
-}
-
 template <typename T>
 __global__ __launch_bounds__(QUERY_THREADS) void query_kernel(QueryParams p)
 {
@@ -70,7 +57,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void query_kernel(QueryParams p)
         double o[4] = {nan, nan, nan, nan};
         if (ok) {
             pll_block<T>(pv, 2 * j, 2 * j, o);
-            query_round<T>(p, pv.ex, o);
+            query_round<T>(p.bf != 0, pv.ex, o);
         }
         double* blk = p.blocks + ((size_t)row * K + k) * 4;
         double* cr = p.cross + ((size_t)row * K + k) * 6;
@@ -104,7 +91,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void query_kernel(QueryParams p)
         double o[4] = {nan, nan, nan, nan};
         if (ja >= 0 && ja < d.N && jb >= 0 && jb < d.N) {
             pll_block<T>(pv, 2 * ja, 2 * jb, o);
-            query_round<T>(p, pv.ex, o);
+            query_round<T>(p.bf != 0, pv.ex, o);
         }
         double* c0 = cov + (3 + 2 * (size_t)a) * nq + 3 + 2 * (size_t)b;
         c0[0] = o[0];

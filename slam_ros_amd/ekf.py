@@ -43,6 +43,7 @@ EXPORTED = [
     "ekf_predict", "ekf_update", "ekf_read_results", "ekf_upload_state", "ekf_download_state",
     "ekf_init_lowrank", "ekf_storage_exponent", "ekf_rescale", "ekf_get_pose_cov", "ekf_get_ellipse", "ekf_ellipse_of_block",
     "ekf_query_joint", "ekf_query_marginals", "ekf_query_joint_device",
+    "ekf_gate_lines", "ekf_gate_lines_device",
     "ekf_landmark_block_bytes",
     "ekf_state_dim", "ekf_profile_enable", "ekf_profile_read", "ekf_profile_flushes",
     "ekf_flush_kernel_name", "ekf_debug_scan_stamps", "ekf_debug_result_words",
@@ -77,8 +78,20 @@ class EkfResult(ctypes.Structure):
     ]
 
 
+class EkfGateHit(ctypes.Structure):
+    """ekf_gate_hit (slam_ekf.h): one trial line against the map."""
+    _fields_ = [
+        ("first", ctypes.c_int32), ("nearest", ctypes.c_int32), ("npass", ctypes.c_int32),
+        ("status", ctypes.c_int32), ("d2_first", ctypes.c_double), ("d2_nearest", ctypes.c_double),
+        ("S", ctypes.c_double * 4), ("v", ctypes.c_double * 2),
+    ]
+
+
+ekf_gate_hit = EkfGateHit   # (the C name)
+
+
 class EkfError(RuntimeError):
-    pass
+    code = 0   # the EKF_E* status of the failed call
 
 
 _lib = None
@@ -131,6 +144,8 @@ def load_library(path: str = ""):
         "ekf_query_joint": (ctypes.c_int, [vp, ctypes.c_int, ip, ctypes.c_int, dp, dp]),
         "ekf_query_marginals": (ctypes.c_int, [vp, ctypes.c_int, ip, ctypes.c_int, dp, dp, dp]),
         "ekf_query_joint_device": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp]),
+        "ekf_gate_lines": (ctypes.c_int, [vp, ctypes.c_int, dp, vp, ctypes.c_int, vp, dp]),
+        "ekf_gate_lines_device": (ctypes.c_int, [vp, vp, vp, vp, vp, vp]),
         "ekf_landmark_block_bytes": (sz, [vp]),
         "ekf_state_dim": (ctypes.c_int, [vp]),
         "ekf_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
@@ -166,7 +181,9 @@ def load_library(path: str = ""):
 def _check(rc: int, what: str):
     if rc != 0:
         msg = load_library().ekf_strerror(rc).decode()
-        raise EkfError(f"{what}: {msg} ({rc})")
+        err = EkfError(f"{what}: {msg} ({rc})")
+        err.code = rc
+        raise err
 
 
 def _dp(a):
@@ -383,6 +400,36 @@ class Ensemble:
                                                 ctypes.c_void_p(d_cov or None), ctypes.c_void_p(d_mean or None)),
                "ekf_query_joint_device")
 
+    def gate_lines(self, e: int, lines, encoder=None, distances: bool = False):
+        """Trial lines scored against instance e's map, state untouched (slam_ekf.h ekf_gate_lines):
+        every line on its own, as the first line of a scan. encoder given: the predict is applied on
+        read, so hits[0]["first"] is the match localize(encoder, lines) would report for line 0; None:
+        the committed pose and strip (between predict and update: what update would use). Returns a
+        list of dicts (first, nearest, npass, status, d2_first, d2_nearest, S [2, 2], v [2]), and
+        with distances=True also d2 [L, N] (+inf at and past savedLineCount)."""
+        la = np.ascontiguousarray(np.asarray(lines, dtype=np.float64).reshape(-1, 6))
+        L = int(la.shape[0])
+        enc = None if encoder is None else np.ascontiguousarray(np.asarray(encoder, dtype=np.float64).reshape(3))
+        hits = (EkfGateHit * max(L, 1))()
+        d2 = np.zeros((L, self.capacity)) if distances else None
+        _check(self._lib.ekf_gate_lines(self._h, int(e), _dp(enc), la.ctypes.data_as(ctypes.c_void_p), L,
+                                        ctypes.byref(hits), _dp(d2)), "ekf_gate_lines")
+        out = [self._hit(hits[i]) for i in range(L)]
+        return (out, d2) if distances else out
+
+    @staticmethod
+    def _hit(h) -> dict:
+        return dict(first=h.first, nearest=h.nearest, npass=h.npass, status=h.status, d2_first=h.d2_first,
+                    d2_nearest=h.d2_nearest, S=np.array(h.S[:]).reshape(2, 2), v=np.array(h.v[:]))
+
+    def gate_lines_device(self, d_enc: int, d_lines: int, d_nlines: int, d_hits: int, d_d2: int = 0):
+        """The gate of every instance at once, buffers in device memory (raw pointers: enc [E, 3] or 0,
+        lines [E, max_lines] ekf_line, nlines [E] int32, hits [E, max_lines] ekf_gate_hit, d2
+        [E, max_lines, N] or 0); asynchronous on the context stream."""
+        _check(self._lib.ekf_gate_lines_device(self._h, ctypes.c_void_p(d_enc or None), ctypes.c_void_p(d_lines or None),
+                                               ctypes.c_void_p(d_nlines or None), ctypes.c_void_p(d_hits or None),
+                                               ctypes.c_void_p(d_d2 or None)), "ekf_gate_lines_device")
+
     def ellipse(self, e: int = 0):
         axii = (ctypes.c_float * 2)()
         ang = ctypes.c_float()
@@ -501,6 +548,13 @@ class Robot:
         rows, intervals = self._as_rows(lines)
         res = self._ens.update(rows[None], [len(rows)])[0]
         self._commit(res, intervals)
+
+    def gateLines(self, lines, encoder=None):
+        """Which landmark localize would pick for each line taken alone, how far away it is and
+        whether a second one passes (the reference has no such member: its association is first-fit
+        inside localize, Robot.cpp:313-498). The state is untouched. See Ensemble.gate_lines."""
+        rows, _ = self._as_rows(lines)
+        return self._ens.gate_lines(0, rows, encoder)
 
     def getEllipse(self):
         ok, axii, angle = self._ens.ellipse(0)

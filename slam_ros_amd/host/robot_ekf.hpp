@@ -139,6 +139,23 @@ public:
         return ekf_ellipse_of_block(blk, axii, angle) == 1;
     }
 
+    // Which landmark localize would pick for each line taken alone (as the first line of a scan), how
+    // far away it is and whether a second one passes the gate (the reference has no such member: its
+    // association is first-fit inside localize, Robot.cpp:313-498). Nothing of the state changes and
+    // the deferred flush is not drained (ekf_gate_lines). encoder given: the predict is applied on
+    // read, so hits[0].first is the match localize(lines, rot, encoder) would report for line 0;
+    // nullptr: the committed pose (between predict and update: what update would use).
+    bool gateLines(const std::vector<Line>& lines, std::vector<ekf_gate_hit>& hits, const double* encoder = nullptr)
+    {
+        std::vector<ekf_line> buf;
+        if (!pack(lines, buf)) return false;
+        hits.assign(lines.size() ? lines.size() : 1, ekf_gate_hit{});
+        const bool ok = report(ekf_gate_lines(ctx_, 0, encoder, buf.data(), (int)lines.size(), hits.data(), nullptr),
+                               "ekf_gate_lines");
+        hits.resize(lines.size());
+        return ok;
+    }
+
     void normalizeRadian(double& rad) { normalize_radian(rad); }
 
     void setMirror(Mirror m)
