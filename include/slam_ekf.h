@@ -39,7 +39,8 @@ extern "C" {
  *    EKF_DD_BLOCKS_PER_CU, EKF_FLUSH_VARIANT); EKF_ARITH_F16X3; the row shard replaced by a
  *    partitioned instance (ekf_shard_create ... ekf_shard_end: tiles partitioned, O(n) state
  *    replicated). Added since, with the number unchanged (entry points only): ekf_query_joint,
- *    ekf_query_marginals, ekf_query_joint_device; ekf_gate_lines, ekf_gate_lines_device. */
+ *    ekf_query_marginals, ekf_query_joint_device; ekf_gate_lines, ekf_gate_lines_device;
+ *    ekf_gate_joint, ekf_gate_joint_device. */
 #define SLAM_EKF_ABI_VERSION 3
 #define EKF_MAX_LINES 64 /* lines per scan per instance; main.cpp:99 reserves 20 */
 
@@ -371,6 +372,49 @@ int ekf_gate_lines(ekf_ctx* ctx, int e, const double enc[3] /* may be NULL */, c
 int ekf_gate_lines_device(ekf_ctx* ctx, const double* d_enc /* [E][3] or NULL */,
                           const ekf_line* d_lines /* [E][max_lines] */, const int32_t* d_nlines /* [E] */,
                           ekf_gate_hit* d_hits /* [E][max_lines] */, double* d_d2 /* [E][max_lines][N] or NULL */);
+
+/* Joint compatibility of line-landmark hypotheses, state untouched: the squared Mahalanobis distance
+ * and the log determinant of the stacked innovation of a whole assignment. ekf_gate_lines scores each
+ * line alone; two pairings that pass alone can be jointly impossible, because their innovations are
+ * correlated through the pose and the landmark-landmark blocks of P. The reference has no such
+ * member (its association, Robot.cpp:313-498, is first-fit).
+ * Hypothesis: assign[h][i] is the landmark of line i, or -1 for "unassigned" (the line is left out).
+ *   The m assigned lines enter v (2m long) in list order. The same landmark on two lines is allowed
+ *   (R keeps S definite). A landmark in [savedLineCount, N) reads as the zero rows the state holds,
+ *   as for the covariance queries.
+ * v, H, R per line: exactly what the association and ekf_gate_lines use for (line i, landmark j): the
+ *   wrapped angle innovation, H, and R of index i under the context's r_mode. d2_each[h][i] is that
+ *   pair's own distance, bit for bit ekf_gate_lines' d2[i][assign[h][i]] for a saved landmark, NaN
+ *   where the line is unassigned.
+ * S: the 2x2 block (a, b) is H_a P[{0,1,2,l_a},{0,1,2,l_b}] H_b^T, plus R_a when a == b, from the 3x3
+ *   robot block, the two landmarks' strip columns and the block P[l_a, l_b], the last read as the
+ *   covariance queries read it (pending steps applied on read). The lower triangle is computed and
+ *   factored by Cholesky in fp64, in a fixed order: a hit depends only on its own hypothesis and the
+ *   state, not on H, its place in the list, or the host / device form.
+ * Result: d2 = v^T S^-1 v and logdet = log det S. The log-likelihood of the scan under the
+ *   hypothesis is the caller's to form: -(d2 + logdet) / 2 - m log(2 pi).
+ * Pose and P: the three cases of ekf_gate_lines (enc given: predict on read; NULL between ekf_predict
+ *   and ekf_update: the predicted strip and x_pre; NULL otherwise: the committed pose), and its
+ *   EKF_EINVAL for enc != NULL between ekf_predict and ekf_update.
+ * No drain, no state change, as ekf_gate_lines. The host form is synchronous: one kernel, one copy,
+ *   one wait on the context stream. The device form only enqueues.
+ * Errors: as ekf_gate_lines, plus EKF_ERANGE for H < 0 or an assign entry outside [-1, N). In the
+ *   device form such an entry is never dereferenced: that hypothesis gets d2 = logdet = NaN and
+ *   EKF_ST_SINGULAR_S (d2_each NaN), the others are unaffected; entries i >= nlines[e] are ignored.
+ *   H == 0 and L == 0 are valid. EKF_EINVAL for a partitioned context. */
+typedef struct ekf_joint_hit {
+    int32_t m;        /* lines of the hypothesis that carry a landmark */
+    int32_t status;   /* EKF_ST_SINGULAR_S: a pivot of the factorisation of S was <= 0 or not finite (d2, logdet NaN) */
+    double d2;        /* v^T S^-1 v of the stacked innovation, 2m long; 0 for m == 0 */
+    double logdet;    /* log det S; 0 for m == 0 */
+} ekf_joint_hit;
+int ekf_gate_joint(ekf_ctx* ctx, int e, const double enc[3] /* may be NULL */, const ekf_line* lines, int L,
+                   const int32_t* assign /* [H][L] */, int H, ekf_joint_hit* hits /* [H] */,
+                   double* d2_each /* [H][L], may be NULL */);
+/* Every instance at once, all buffers in device memory, asynchronous on the context stream. */
+int ekf_gate_joint_device(ekf_ctx* ctx, const double* d_enc /* [E][3] or NULL */, const ekf_line* d_lines /* [E][max_lines] */,
+                          const int32_t* d_nlines /* [E] */, const int32_t* d_assign /* [E][H][max_lines] */, int H,
+                          ekf_joint_hit* d_hits /* [E][H] */, double* d_d2_each /* [E][H][max_lines] or NULL */);
 
 /* One instance with its landmark block partitioned over ranks, for maps
  * whose packed P should not (or cannot) live on one GPU. No reference member maps to these: they

@@ -14,7 +14,7 @@
 //     next group's scans run on S reading X[in] — the output of flush f-1 — with the steps of
 //     groups f and f+1 pending (< 2T); R = 2T.
 // Any call that reads the whole landmark block or replaces it drains (flushes the partial group,
-// syncs); the covariance queries (ekf_query_*) and the gate query (ekf_gate_lines*) read chosen
+// syncs); the covariance queries (ekf_query_*) and the gate queries (ekf_gate_lines*, ekf_gate_joint*) read chosen
 // blocks as an association kernel would, with the pending steps applied on read, and leave the
 // schedule as it is.
 #include <hip/hip_runtime.h>
@@ -1776,6 +1776,94 @@ extern "C" int ekf_gate_lines_device(ekf_ctx* c, const double* d_enc, const ekf_
     gp.hits = d_hits;
     gp.d2 = d_d2;
     return enqueue_gate(c, gp);
+}
+
+// ---- joint compatibility of hypotheses (slam_ekf.h ekf_gate_joint; kernel: unit_joint.hip) ----
+// The gate's view and hazard handling, one launch on S; the kernel's only scratch is its LDS.
+static int enqueue_joint(ekf_ctx* c, ekf::JointParams& jp)
+{
+    const int rc = begin_read(c, jp);
+    if (rc) return rc;
+    jp.pose = c->pose;
+    jp.xpre = c->xpre;
+    jp.saved = c->saved;
+    jp.use_xpre = c->predicted;
+    jp.r_mode = c->cfg.r_mode;
+    jp.gate = c->cfg.mahalanobis;
+    jp.enc_noise = c->cfg.encoder_noise;
+    HIP_TRY(ekf::launch_joint(jp, c->cfg.precision, c->stream));
+    return end_read(c);
+}
+
+extern "C" int ekf_gate_joint(ekf_ctx* c, int e, const double enc[3], const ekf_line* lines, int L,
+                              const int32_t* assign, int H, ekf_joint_hit* hits, double* d2_each)
+{
+    if (!c || c->sh_world > 0) return EKF_EINVAL;
+    if (e < 0 || e >= c->cfg.instances || L < 0 || L > c->d.max_lines || H < 0) return EKF_ERANGE;
+    if ((L > 0 && !lines) || (H > 0 && !hits) || (H > 0 && L > 0 && !assign)) return EKF_EINVAL;
+    if (enc && c->predicted) return EKF_EINVAL;   // the committed strip is already the predicted one
+    const size_t HL = (size_t)H * L;
+    for (size_t k = 0; k < HL; k++)
+        if (assign[k] < -1 || assign[k] >= c->d.N) return EKF_ERANGE;
+    if (H == 0) return EKF_OK;
+    if (L == 0) {   // every hypothesis is empty
+        for (int h = 0; h < H; h++) hits[h] = ekf_joint_hit{0, 0, 0.0, 0.0};
+        return EKF_OK;
+    }
+    // device scratch [hits | d2_each], the pinned buffer [hits | d2_each | lines | enc | assign]
+    const size_t nh = sizeof(ekf_joint_hit) * (size_t)H;
+    const size_t nd = d2_each ? sizeof(double) * HL : 0;
+    const size_t nl = sizeof(ekf_line) * (size_t)L;
+    const size_t na = sizeof(int32_t) * HL;
+    int rc = query_buffers(c, nh + nd, nl + 3 * sizeof(double) + na);
+    if (rc) return rc;
+    memcpy(c->q_host + nh + nd, lines, nl);
+    if (enc) memcpy(c->q_host + nh + nd + nl, enc, 3 * sizeof(double));
+    memcpy(c->q_host + nh + nd + nl + 3 * sizeof(double), assign, na);
+    ekf::JointParams jp;
+    memset(&jp, 0, sizeof(jp));
+    jp.E = 1;
+    jp.e0 = e;
+    jp.L = L;
+    jp.H = H;
+    jp.astride = L;
+    jp.lines = reinterpret_cast<const ekf_line*>(c->q_host_dev + nh + nd);
+    jp.enc = enc ? reinterpret_cast<const double*>(c->q_host_dev + nh + nd + nl) : nullptr;
+    jp.assign = reinterpret_cast<const int32_t*>(c->q_host_dev + nh + nd + nl + 3 * sizeof(double));
+    char* dev = reinterpret_cast<char*>(c->q_dev);
+    jp.hits = reinterpret_cast<ekf_joint_hit*>(dev);
+    jp.d2_each = d2_each ? reinterpret_cast<double*>(dev + nh) : nullptr;
+    rc = enqueue_joint(c, jp);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->q_host, c->q_dev, nh + nd, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memcpy(hits, c->q_host, nh);
+    if (d2_each) memcpy(d2_each, c->q_host + nh, nd);
+    return EKF_OK;
+}
+
+extern "C" int ekf_gate_joint_device(ekf_ctx* c, const double* d_enc, const ekf_line* d_lines, const int32_t* d_nlines,
+                                     const int32_t* d_assign, int H, ekf_joint_hit* d_hits, double* d_d2_each)
+{
+    if (!c || c->sh_world > 0) return EKF_EINVAL;
+    if (H < 0) return EKF_ERANGE;
+    if (!d_lines || !d_nlines || (H > 0 && (!d_assign || !d_hits))) return EKF_EINVAL;
+    if (d_enc && c->predicted) return EKF_EINVAL;
+    if (H == 0) return EKF_OK;
+    ekf::JointParams jp;
+    memset(&jp, 0, sizeof(jp));
+    jp.E = c->cfg.instances;
+    jp.e0 = 0;
+    jp.L = 0;
+    jp.H = H;
+    jp.astride = c->d.max_lines;
+    jp.enc = d_enc;
+    jp.lines = d_lines;
+    jp.nlines = d_nlines;
+    jp.assign = d_assign;
+    jp.hits = d_hits;
+    jp.d2_each = d_d2_each;
+    return enqueue_joint(c, jp);
 }
 
 extern "C" size_t ekf_landmark_block_bytes(const ekf_ctx* c)

@@ -29,7 +29,8 @@
 // the partitioned instance), ekf_gate.h (the gate arithmetic of one candidate, shared with the gate
 // query), ekf_flush_common.h and one ekf_flush_*.h per flush family, ekf_pack.h;
 // unit_query.hip holds the covariance queries' kernel (pll_block on chosen landmarks), unit_gate.hip
-// the gate query's two kernels (trial lines against every saved landmark, state untouched).
+// the gate query's two kernels (trial lines against every saved landmark, state untouched),
+// unit_joint.hip the joint gate's kernel (a hypothesis' stacked innovation, Cholesky in LDS).
 // Each unit_*.hip includes what its launchers instantiate (build.py: UNITS).
 #pragma once
 

@@ -327,6 +327,44 @@ struct GateParams {
 };
 hipError_t launch_gate(const GateParams& p, int precision, hipStream_t st);
 
+// Joint compatibility of hypotheses (unit_joint.hip): per launch row (instance e0 + row) H assignments
+// of the row's lines to landmarks; the view of GateParams (the same preamble), one workgroup per
+// (hypothesis, row). assign and d2_each are `astride` apart per hypothesis (L in the host form,
+// max_lines in the device form); the kernel needs no scratch but its LDS.
+constexpr int JOINT_THREADS = 256;
+struct JointParams {
+    Dims d;
+    int E;                // instances in this launch (grid.y)
+    int e0;               // first instance of this launch
+    int Etot;             // instances of the context
+    int usym;             // symmetric fp32 operands (ScanParams::usym)
+    int bf;               // split-plane context: fp16 storage rounded once, after the pending steps
+    int npend;            // steps not yet in Pread, applied on read (in order)
+    const void* Pread;    // [Etot][ntiles][1024]
+    const double* Rs;     // [2][Etot][3][n]
+    const double* y;      // [2][Etot][n]
+    const int* live;      // [Etot]
+    const int* pexp;      // [Etot]
+    const double* pose;   // [Etot][3] committed pose
+    const double* xpre;   // [Etot][3] x_pre of the last ekf_predict
+    const int* saved;     // [Etot]
+    int use_xpre;         // enc == nullptr: 1 between ekf_predict and ekf_update (x_pre), 0 the pose
+    int r_mode;
+    int L;                // lines of every row (nlines == nullptr: the host form)
+    int H;                // hypotheses per row (grid.x)
+    int astride;          // entries per hypothesis in assign and d2_each
+    double gate, enc_noise;
+    const double* enc;    // [E][3] (per launch row) the predict is applied on read; nullptr: no motion
+    const ekf_line* lines;// [E][max_lines]
+    const int* nlines;    // [E], or nullptr (the host form)
+    const int32_t* assign;// [E][H][astride]
+    ekf_joint_hit* hits;  // [E][H]
+    double* d2_each;      // [E][H][astride] or nullptr
+    Slot pend[PMAX];      // pending steps, oldest first
+};
+hipError_t launch_joint(const JointParams& p, int precision, hipStream_t st);
+size_t joint_lds_bytes(int max_lines);   // dynamic LDS of the joint kernel (the packed factor)
+
 hipError_t launch_scan(const ScanParams& p, int precision, hipStream_t st);
 int scan_blocks_per_cu(int precision);
 size_t scan_lds_bytes(int precision);   // static LDS of the association kernel

@@ -15,50 +15,6 @@
 
 namespace ekf {
 
-// x_pre, F3 and the predicted 3×3 block of instance e from the committed pose and strip
-// (Robot.cpp:130-258), expression for expression the PHASE_PREDICT branch of scan_kernel, so that a
-// gate with an encoder pose sees what ekf_predict would commit, bit for bit
-__device__ __forceinline__ void gate_predict(const GateParams& p, int e, const double* enc, double R33[9],
-                                             double xp[3], double F3[9])
-{
-    const double x0 = p.pose[3 * e + 0], y0 = p.pose[3 * e + 1], t0 = p.pose[3 * e + 2];
-    const double u2 = t0 - enc[2];
-    const double dx = x0 - enc[0], dy = y0 - enc[1];
-    const double u0 = sqrt(dx * dx + dy * dy);
-    const double c = u2 / 2.0 + t0;
-    double sc, cc;
-    sincos(c, &sc, &cc);
-    F3[2] = -u0 * sc;
-    F3[5] = u0 * cc;
-    xp[0] = x0 + u0 * cc;
-    xp[1] = y0 + u0 * sc;
-    xp[2] = t0 + u2;
-    const double Fu3[9] = {cc, 0, -u0 * sc / 2.0, sc, 1, u0 * cc / 2.0, 0, 0, 1};
-    const double qs = (-1.0 / (1 + fabs(u0)) + 1);
-    const double Q[9] = {p.enc_noise * qs, 0, 0, 0, 2 * p.enc_noise * qs, 0, 0, 0,
-                         p.enc_noise * qs};
-    double FP[9], FuQ[9];
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) {
-            double s = 0.0, t = 0.0;
-            for (int k = 0; k < 3; k++) {
-                s += F3[a * 3 + k] * R33[k * 3 + b];
-                t += Fu3[a * 3 + k] * Q[k * 3 + b];
-            }
-            FP[a * 3 + b] = s;
-            FuQ[a * 3 + b] = t;
-        }
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) {
-            double s = 0.0, t = 0.0;
-            for (int k = 0; k < 3; k++) {
-                s += FP[a * 3 + k] * F3[b * 3 + k];
-                t += FuQ[a * 3 + k] * Fu3[b * 3 + k];
-            }
-            R33[a * 3 + b] = s + t;
-        }
-}
-
 // the lowest lane of a wave's ballot, or 64
 __device__ __forceinline__ int first_lane(unsigned long long m) { return m ? __ffsll((long long)m) - 1 : 64; }
 

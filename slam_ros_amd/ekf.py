@@ -43,7 +43,7 @@ EXPORTED = [
     "ekf_predict", "ekf_update", "ekf_read_results", "ekf_upload_state", "ekf_download_state",
     "ekf_init_lowrank", "ekf_storage_exponent", "ekf_rescale", "ekf_get_pose_cov", "ekf_get_ellipse", "ekf_ellipse_of_block",
     "ekf_query_joint", "ekf_query_marginals", "ekf_query_joint_device",
-    "ekf_gate_lines", "ekf_gate_lines_device",
+    "ekf_gate_lines", "ekf_gate_lines_device", "ekf_gate_joint", "ekf_gate_joint_device",
     "ekf_landmark_block_bytes",
     "ekf_state_dim", "ekf_profile_enable", "ekf_profile_read", "ekf_profile_flushes",
     "ekf_flush_kernel_name", "ekf_debug_scan_stamps", "ekf_debug_result_words",
@@ -88,6 +88,16 @@ class EkfGateHit(ctypes.Structure):
 
 
 ekf_gate_hit = EkfGateHit   # (the C name)
+
+
+class EkfJointHit(ctypes.Structure):
+    """ekf_joint_hit (slam_ekf.h): one hypothesis' stacked innovation against the map."""
+    _fields_ = [
+        ("m", ctypes.c_int32), ("status", ctypes.c_int32), ("d2", ctypes.c_double), ("logdet", ctypes.c_double),
+    ]
+
+
+ekf_joint_hit = EkfJointHit   # (the C name)
 
 
 class EkfError(RuntimeError):
@@ -146,6 +156,8 @@ def load_library(path: str = ""):
         "ekf_query_joint_device": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp]),
         "ekf_gate_lines": (ctypes.c_int, [vp, ctypes.c_int, dp, vp, ctypes.c_int, vp, dp]),
         "ekf_gate_lines_device": (ctypes.c_int, [vp, vp, vp, vp, vp, vp]),
+        "ekf_gate_joint": (ctypes.c_int, [vp, ctypes.c_int, dp, vp, ctypes.c_int, vp, ctypes.c_int, vp, dp]),
+        "ekf_gate_joint_device": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, vp, vp]),
         "ekf_landmark_block_bytes": (sz, [vp]),
         "ekf_state_dim": (ctypes.c_int, [vp]),
         "ekf_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
@@ -430,6 +442,40 @@ class Ensemble:
                                                ctypes.c_void_p(d_nlines or None), ctypes.c_void_p(d_hits or None),
                                                ctypes.c_void_p(d_d2 or None)), "ekf_gate_lines_device")
 
+    def gate_joint(self, e: int, lines, assign, encoder=None, each: bool = False):
+        """Joint compatibility of hypotheses against instance e's map, state untouched (slam_ekf.h
+        ekf_gate_joint). assign [H, L] int32: the landmark of each line or -1. Returns a list of H dicts
+        (m, status, d2, logdet): d2 = v^T S^-1 v of the stacked innovation, logdet = log det S; the
+        log-likelihood is -(d2 + logdet) / 2 - m log(2 pi). With each=True also d2_each [H, L], every
+        pair's own distance (NaN where unassigned). encoder as for gate_lines."""
+        la = np.ascontiguousarray(np.asarray(lines, dtype=np.float64).reshape(-1, 6))
+        L = int(la.shape[0])
+        aa = np.ascontiguousarray(np.asarray(assign, dtype=np.int32).reshape(-1, L) if L else
+                                  np.zeros((len(assign), 0), dtype=np.int32))
+        H = int(aa.shape[0])
+        enc = None if encoder is None else np.ascontiguousarray(np.asarray(encoder, dtype=np.float64).reshape(3))
+        hits = (EkfJointHit * max(H, 1))()
+        d2 = np.zeros((H, L)) if each else None
+        _check(self._lib.ekf_gate_joint(self._h, int(e), _dp(enc), la.ctypes.data_as(ctypes.c_void_p), L,
+                                        aa.ctypes.data_as(ctypes.c_void_p), H, ctypes.byref(hits), _dp(d2)),
+               "ekf_gate_joint")
+        out = [self._joint_hit(hits[h]) for h in range(H)]
+        return (out, d2) if each else out
+
+    @staticmethod
+    def _joint_hit(h) -> dict:
+        return dict(m=h.m, status=h.status, d2=h.d2, logdet=h.logdet)
+
+    def gate_joint_device(self, d_enc: int, d_lines: int, d_nlines: int, d_assign: int, H: int, d_hits: int,
+                          d_d2_each: int = 0):
+        """The hypotheses of every instance at once, buffers in device memory (raw pointers: enc [E, 3]
+        or 0, lines [E, max_lines] ekf_line, nlines [E] int32, assign [E, H, max_lines] int32, hits
+        [E, H] ekf_joint_hit, d2_each [E, H, max_lines] or 0); asynchronous on the context stream."""
+        _check(self._lib.ekf_gate_joint_device(self._h, ctypes.c_void_p(d_enc or None), ctypes.c_void_p(d_lines or None),
+                                               ctypes.c_void_p(d_nlines or None), ctypes.c_void_p(d_assign or None), int(H),
+                                               ctypes.c_void_p(d_hits or None), ctypes.c_void_p(d_d2_each or None)),
+               "ekf_gate_joint_device")
+
     def ellipse(self, e: int = 0):
         axii = (ctypes.c_float * 2)()
         ang = ctypes.c_float()
@@ -555,6 +601,13 @@ class Robot:
         inside localize, Robot.cpp:313-498). The state is untouched. See Ensemble.gate_lines."""
         rows, _ = self._as_rows(lines)
         return self._ens.gate_lines(0, rows, encoder)
+
+    def gateJoint(self, lines, assign, encoder=None, each=False):
+        """Joint compatibility of hypotheses (assign [H, L]: the landmark of each line or -1): per
+        hypothesis the stacked innovation's v^T S^-1 v and log det S (the reference has no such
+        member). The state is untouched. See Ensemble.gate_joint."""
+        rows, _ = self._as_rows(lines)
+        return self._ens.gate_joint(0, rows, assign, encoder, each)
 
     def getEllipse(self):
         ok, axii, angle = self._ens.ellipse(0)

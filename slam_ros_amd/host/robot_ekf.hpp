@@ -156,6 +156,25 @@ public:
         return ok;
     }
 
+    // Joint compatibility of hypotheses: assign holds, per hypothesis, the landmark of each line or -1
+    // (assign.size() == H * lines.size()); per hypothesis the stacked innovation's vT S^-1 v and
+    // log det S (ekf_gate_joint; the log-likelihood is -(d2 + logdet) / 2 - m log 2 pi). The state is
+    // untouched and the deferred flush is not drained. encoder as for gateLines.
+    bool gateJoint(const std::vector<Line>& lines, const std::vector<int32_t>& assign, std::vector<ekf_joint_hit>& hits,
+                   const double* encoder = nullptr)
+    {
+        std::vector<ekf_line> buf;
+        if (!pack(lines, buf)) return false;
+        const size_t L = lines.size();
+        if (L == 0 || assign.size() % L) return false;
+        const size_t H = assign.size() / L;
+        hits.assign(H ? H : 1, ekf_joint_hit{});
+        const bool ok = report(ekf_gate_joint(ctx_, 0, encoder, buf.data(), (int)L, assign.data(), (int)H, hits.data(), nullptr),
+                               "ekf_gate_joint");
+        hits.resize(H);
+        return ok;
+    }
+
     void normalizeRadian(double& rad) { normalize_radian(rad); }
 
     void setMirror(Mirror m)
