@@ -40,7 +40,7 @@ extern "C" {
  *    partitioned instance (ekf_shard_create ... ekf_shard_end: tiles partitioned, O(n) state
  *    replicated). Added since, with the number unchanged (entry points only): ekf_query_joint,
  *    ekf_query_marginals, ekf_query_joint_device; ekf_gate_lines, ekf_gate_lines_device;
- *    ekf_gate_joint, ekf_gate_joint_device. */
+ *    ekf_gate_joint, ekf_gate_joint_device; ekf_resample, ekf_copy_instance. */
 #define SLAM_EKF_ABI_VERSION 3
 #define EKF_MAX_LINES 64 /* lines per scan per instance; main.cpp:99 reserves 20 */
 
@@ -415,6 +415,33 @@ int ekf_gate_joint(ekf_ctx* ctx, int e, const double enc[3] /* may be NULL */, c
 int ekf_gate_joint_device(ekf_ctx* ctx, const double* d_enc /* [E][3] or NULL */, const ekf_line* d_lines /* [E][max_lines] */,
                           const int32_t* d_nlines /* [E] */, const int32_t* d_assign /* [E][H][max_lines] */, int H,
                           ekf_joint_hit* d_hits /* [E][H] */, double* d_d2_each /* [E][H][max_lines] or NULL */);
+
+/* Instances copied onto others on the device: what acts on the weights the queries and gates give
+ * (fork a hypothesis; drop the unlikely instances of an ensemble and duplicate the likely ones). The
+ * reference has one filter and no such member.
+ * Instance e takes the whole state of instance src[e]; src[e] == e keeps it. Afterwards every read
+ *   entry point (ekf_download_state, ekf_get_pose_cov, ekf_get_ellipse, ekf_query_*, ekf_gate_lines,
+ *   ekf_gate_joint, ekf_storage_exponent, ekf_read_results: the source's last result record) returns
+ *   for e what it returns for src[e], bit for bit, and fed the same scans e produces the same bits as
+ *   src[e] from then on, under every precision, arithmetic, schedule and option.
+ * Sources are fixed points: src[src[e]] == src[e] for every e (survivors stay where they are, dead
+ *   slots are overwritten: what a resampler produces), else EKF_EINVAL. No slice of the state is then
+ *   both read and written, so the copy is one launch with no ordering and no staging.
+ * No drain, no flush, no step: the steps pending in the flush group travel with the instance (their
+ *   ring slots are copied), the schedule is untouched, and an instance with src[e] == e is afterwards
+ *   bit-identical to the same instance of a context that never made the call, also on the split
+ *   arithmetics (where a drain would change every instance's bits). ekf_download_state /
+ *   ekf_upload_state do the same through the dense n x n matrix on the host, with two drains and a
+ *   re-rounding of the block.
+ * Asynchronous on the context stream, behind every scan enqueued so far; src is a host list, read
+ *   before the call returns.
+ * Errors: EKF_EINVAL for a NULL context or list, a source that is not a fixed point, a partitioned
+ *   context, or a call between ekf_predict and ekf_update; EKF_ERANGE for an entry outside [0, E).
+ *   The identity list is valid and launches nothing. */
+int ekf_resample(ekf_ctx* ctx, const int32_t* src /* [E], host */);
+/* ekf_resample with src = identity except src[dst] = from (from must keep its state: always true
+ * here). EKF_ERANGE for dst or from outside [0, E); dst == from is valid and launches nothing. */
+int ekf_copy_instance(ekf_ctx* ctx, int dst, int from);
 
 /* One instance with its landmark block partitioned over ranks, for maps
  * whose packed P should not (or cannot) live on one GPU. No reference member maps to these: they

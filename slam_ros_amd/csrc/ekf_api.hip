@@ -16,7 +16,8 @@
 // Any call that reads the whole landmark block or replaces it drains (flushes the partial group,
 // syncs); the covariance queries (ekf_query_*) and the gate queries (ekf_gate_lines*, ekf_gate_joint*) read chosen
 // blocks as an association kernel would, with the pending steps applied on read, and leave the
-// schedule as it is.
+// schedule as it is. ekf_resample copies instances onto others with their pending steps, mid-group,
+// and leaves it as it is too.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -34,6 +35,7 @@
 
 #include "../../include/slam_ekf.h"
 #include "ekf_kernels.h"
+#include "ekf_resample_plan.h"
 
 using ekf::Dims;
 
@@ -74,6 +76,13 @@ struct ekf_ctx {
     unsigned char* g_flags = nullptr;
     ekf::GatePart* g_part = nullptr;
     int predicted = 0;
+    // ekf_resample: the copy table in pinned host memory the kernel reads (sized to the largest call
+    // so far and kept), and the event behind the last launch that reads it
+    ekf::CopySeg* rs_host = nullptr;
+    ekf::CopySeg* rs_host_dev = nullptr;
+    size_t rs_cap = 0;
+    hipEvent_t rs_ev = nullptr;
+    int rs_pending = 0;
     // partitioned instance (ekf_shard_create): rank sh_rank of sh_world stores tile rows [sh_r0, sh_r1);
     // the running scan's replicated state
     int sh_rank = -1, sh_world = 0, sh_r0 = 0, sh_r1 = 0;
@@ -261,6 +270,8 @@ static void free_all(ekf_ctx* c)
     for (void* p : {(void*)c->dbg, (void*)c->dense, (void*)c->q_dev, (void*)c->sh_xbuf, (void*)c->sh_xcols})
         (void)hipFree(p);   // (or null)
     if (c->q_host) (void)hipHostFree(c->q_host);
+    if (c->rs_host) (void)hipHostFree(c->rs_host);
+    if (c->rs_ev) (void)hipEventDestroy(c->rs_ev);
     for (void* p : c->pinned_mem) (void)hipHostFree(p);
     if (c->h_agree) (void)hipHostFree(c->h_agree);
     if (c->ev_in) (void)hipEventDestroy(c->ev_in);
@@ -1864,6 +1875,110 @@ extern "C" int ekf_gate_joint_device(ekf_ctx* c, const double* d_enc, const ekf_
     jp.hits = d_hits;
     jp.d2_each = d_d2_each;
     return enqueue_joint(c, jp);
+}
+
+// ---- instances copied onto others (slam_ekf.h ekf_resample; kernel: unit_resample.hip) ----
+// Every per-instance slice the kernels read later goes from instance src[e] to instance e in one
+// launch on S (the table: ekf_resample_plan.h). Nothing of the schedule changes: no flush, no step,
+// no epoch, and not a byte of an instance that keeps its state.
+static ekf::ResampleLayout resample_layout(const ekf_ctx* c)
+{
+    ekf::ResampleLayout L;
+    auto addr = [](const void* p) { return (uint64_t)(uintptr_t)p; };
+    L.d = c->d;
+    L.E = c->cfg.instances;
+    L.xinst_bytes = (uint64_t)c->xinst * c->elem;
+    L.op_elem = (int)c->op_elem;
+    L.usym = usym_of(c);
+    L.npl = c->pmode == EKF_ARITH_F16X3 ? 2 : c->pmode == EKF_ARITH_BF16X6 ? 3 : 0;
+    L.res_stride = ekf::RES_STRIDE;
+    L.sync_stride = c->sync_stride;
+    // pipelined: X[in] (the scans' base) and X[out] (the newest flush's output, the next one's input)
+    L.nX = c->cfg.pipeline ? 2 : 1;
+    L.X[0] = addr(c->X[0]);
+    L.X[1] = addr(c->X[1]);
+    L.Rs = addr(c->Rs);
+    L.y = addr(c->y);
+    L.D = addr(c->D);
+    L.cur = addr(c->cur);
+    L.saved = addr(c->saved);
+    L.pexp = addr(c->pexp);
+    L.psig = addr(c->psig);
+    L.pose = addr(c->pose);
+    L.xpre = addr(c->xpre);
+    L.pvmax = addr(c->pvmax);
+    L.sync = addr(c->sync);
+    L.ops_u = addr(c->ops_u);
+    L.ops_v = addr(c->ops_v);
+    L.ops_b = addr(c->ops_b);
+    L.slot_bytes = (uint64_t)c->slot_bytes;
+    L.bslot_bytes = (uint64_t)c->bslot_bytes;
+    for (const ekf::Slot& sl : c->ring) {
+        L.patch.push_back(addr(sl.patch));
+        L.patch_diag.push_back(addr(sl.patch_diag));
+        L.res.push_back(addr(sl.res));
+    }
+    const long long R = (long long)c->ring.size();
+    for (long long k = c->pend0; k < c->nsteps; k++) L.pending.push_back((int)(k % R));
+    L.newest = c->nsteps > 0 ? (int)((c->nsteps - 1) % R) : -1;
+    return L;
+}
+
+extern "C" int ekf_resample(ekf_ctx* c, const int32_t* src)
+{
+    if (!c || !src || c->sh_world > 0) return EKF_EINVAL;
+    const int E = c->cfg.instances;
+    const int bad = ekf::resample_check(src, E);
+    if (bad) return bad == 2 ? EKF_ERANGE : EKF_EINVAL;
+    if (c->predicted) return EKF_EINVAL;   // the committed strip is the predicted one
+    bool any = false;
+    for (int e = 0; e < E; e++) any = any || src[e] != e;
+    if (!any) return EKF_OK;
+    const std::vector<ekf::CopySeg> table = ekf::resample_plan(ekf::resample_arrays(resample_layout(c)), E, src);
+    // the pinned table is rewritten only after the last launch that reads it
+    if (c->rs_pending) HIP_TRY(hipEventSynchronize(c->rs_ev));
+    c->rs_pending = 0;
+    if (!c->rs_ev) HIP_TRY(hipEventCreateWithFlags(&c->rs_ev, hipEventDisableTiming));
+    if (table.size() > c->rs_cap) {
+        if (c->rs_host) (void)hipHostFree(c->rs_host);
+        c->rs_host = c->rs_host_dev = nullptr;
+        c->rs_cap = 0;
+        if (hipHostMalloc((void**)&c->rs_host, sizeof(ekf::CopySeg) * table.size()) != hipSuccess) {
+            c->rs_host = nullptr;
+            return EKF_ENOMEM;
+        }
+        if (hipHostGetDevicePointer((void**)&c->rs_host_dev, c->rs_host, 0) != hipSuccess) {
+            (void)hipHostFree(c->rs_host);
+            c->rs_host = c->rs_host_dev = nullptr;
+            return EKF_EDEVICE;
+        }
+        c->rs_cap = table.size();
+    }
+    memcpy(c->rs_host, table.data(), sizeof(ekf::CopySeg) * table.size());
+    // X[base] and the ring behind the event guarding them (as enqueue); pipelined: the newest flush
+    // on D reads X[in] and the ring and writes X[out], all of which the copy reads or writes
+    if (c->ev_base) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_base, 0));
+    if (c->cfg.pipeline && c->nflush > 0)
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_flush[(c->nflush - 1) & 1], 0));
+    HIP_TRY(ekf::launch_resample(c->rs_host_dev, (int)table.size(), c->ncu, c->stream));
+    HIP_TRY(hipEventRecord(c->rs_ev, c->stream));
+    c->rs_pending = 1;
+    // the next flush on D waits for the copy too (end_read)
+    if (c->cfg.pipeline) HIP_TRY(hipEventRecord(c->ev_scan, c->stream));
+    for (int e = 0; e < E; e++) c->pexp_h[e] = c->pexp_h[src[e]];   // (a source keeps its own: fixed points)
+    c->mirror_epoch = 0;   // the mirrored robot blocks are stale for the overwritten instances
+    return EKF_OK;
+}
+
+extern "C" int ekf_copy_instance(ekf_ctx* c, int dst, int from)
+{
+    if (!c || c->sh_world > 0) return EKF_EINVAL;
+    const int E = c->cfg.instances;
+    if (dst < 0 || dst >= E || from < 0 || from >= E) return EKF_ERANGE;
+    std::vector<int32_t> src((size_t)E);
+    for (int e = 0; e < E; e++) src[e] = e;
+    src[dst] = from;
+    return ekf_resample(c, src.data());
 }
 
 extern "C" size_t ekf_landmark_block_bytes(const ekf_ctx* c)

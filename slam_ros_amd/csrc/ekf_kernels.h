@@ -365,6 +365,11 @@ struct JointParams {
 hipError_t launch_joint(const JointParams& p, int precision, hipStream_t st);
 size_t joint_lds_bytes(int max_lines);   // dynamic LDS of the joint kernel (the packed factor)
 
+// ekf_resample's segmented copy (unit_resample.hip): the nseg entries of the host-built table
+// (ekf_resample_plan.h, device-readable), grid-strided over at most 32 workgroups per CU
+struct CopySeg;
+hipError_t launch_resample(const CopySeg* table, int nseg, int ncu, hipStream_t st);
+
 hipError_t launch_scan(const ScanParams& p, int precision, hipStream_t st);
 int scan_blocks_per_cu(int precision);
 size_t scan_lds_bytes(int precision);   // static LDS of the association kernel

@@ -44,6 +44,7 @@ EXPORTED = [
     "ekf_init_lowrank", "ekf_storage_exponent", "ekf_rescale", "ekf_get_pose_cov", "ekf_get_ellipse", "ekf_ellipse_of_block",
     "ekf_query_joint", "ekf_query_marginals", "ekf_query_joint_device",
     "ekf_gate_lines", "ekf_gate_lines_device", "ekf_gate_joint", "ekf_gate_joint_device",
+    "ekf_resample", "ekf_copy_instance",
     "ekf_landmark_block_bytes",
     "ekf_state_dim", "ekf_profile_enable", "ekf_profile_read", "ekf_profile_flushes",
     "ekf_flush_kernel_name", "ekf_debug_scan_stamps", "ekf_debug_result_words",
@@ -158,6 +159,8 @@ def load_library(path: str = ""):
         "ekf_gate_lines_device": (ctypes.c_int, [vp, vp, vp, vp, vp, vp]),
         "ekf_gate_joint": (ctypes.c_int, [vp, ctypes.c_int, dp, vp, ctypes.c_int, vp, ctypes.c_int, vp, dp]),
         "ekf_gate_joint_device": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, vp, vp]),
+        "ekf_resample": (ctypes.c_int, [vp, ip]),
+        "ekf_copy_instance": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
         "ekf_landmark_block_bytes": (sz, [vp]),
         "ekf_state_dim": (ctypes.c_int, [vp]),
         "ekf_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
@@ -223,6 +226,32 @@ def ellipse_of_block(P22):
     if rc < 0:
         _check(-rc, "ekf_ellipse_of_block")
     return rc == 1, [axii[0], axii[1]], ang.value
+
+
+def resample_plan(weights, u: float) -> list[int]:
+    """Systematic resampling as a list Ensemble.resample accepts. With the weights normalised by their
+    sum, n_e is the number of points (u + k) / E, k = 0 .. E − 1, in instance e's interval of the
+    cumulative weights. Every e with n_e >= 1 keeps its state (src[e] = e); the slots with n_e == 0, in
+    ascending order, take the surplus copies of the survivors in ascending survivor order."""
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    E = int(w.size)
+    if E == 0 or not np.all(np.isfinite(w)) or np.any(w < 0.0):
+        raise ValueError("resample_plan: the weights must be finite and non-negative")
+    total = float(w.sum())
+    if not (total > 0.0) or not math.isfinite(total):
+        raise ValueError("resample_plan: the weights sum to zero")
+    if not 0.0 <= u < 1.0:
+        raise ValueError("resample_plan: u outside [0, 1)")
+    edges = np.cumsum(w / total)
+    points = (u + np.arange(E)) / E
+    # (every point is below 1: rounding in the sum must not push one past the last positive weight)
+    hit = np.minimum(np.searchsorted(edges, points, side="right"), np.flatnonzero(w > 0.0)[-1])
+    counts = np.bincount(hit, minlength=E)
+    src = list(range(E))
+    surplus = [e for e in range(E) for _ in range(int(counts[e]) - 1)]
+    for slot, e in zip([e for e in range(E) if counts[e] == 0], surplus):
+        src[slot] = e
+    return src
 
 
 class Ensemble:
@@ -475,6 +504,19 @@ class Ensemble:
                                                ctypes.c_void_p(d_nlines or None), ctypes.c_void_p(d_assign or None), int(H),
                                                ctypes.c_void_p(d_hits or None), ctypes.c_void_p(d_d2_each or None)),
                "ekf_gate_joint_device")
+
+    def resample(self, src):
+        """Instance e takes the whole state of instance src[e] on the device, pending steps included,
+        without a drain or a flush (slam_ekf.h ekf_resample). Every source must keep its own state
+        (src[src[e]] == src[e]); resample_plan gives such a list. Asynchronous on the context stream."""
+        sa = np.ascontiguousarray(np.asarray(src, dtype=np.int32).reshape(-1))
+        if sa.size != self.instances:
+            raise ValueError(f"resample: {sa.size} sources for {self.instances} instances")
+        _check(self._lib.ekf_resample(self._h, sa.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "ekf_resample")
+
+    def copy_instance(self, dst: int, src: int):
+        """Instance dst becomes a copy of instance src (ekf_copy_instance): forks a hypothesis."""
+        _check(self._lib.ekf_copy_instance(self._h, int(dst), int(src)), "ekf_copy_instance")
 
     def ellipse(self, e: int = 0):
         axii = (ctypes.c_float * 2)()
