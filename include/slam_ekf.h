@@ -40,7 +40,8 @@ extern "C" {
  *    partitioned instance (ekf_shard_create ... ekf_shard_end: tiles partitioned, O(n) state
  *    replicated). Added since, with the number unchanged (entry points only): ekf_query_joint,
  *    ekf_query_marginals, ekf_query_joint_device; ekf_gate_lines, ekf_gate_lines_device;
- *    ekf_gate_joint, ekf_gate_joint_device; ekf_resample, ekf_copy_instance. */
+ *    ekf_gate_joint, ekf_gate_joint_device; ekf_resample, ekf_copy_instance;
+ *    ekf_instance_image_bytes, ekf_export_instances(_device), ekf_import_instances(_device). */
 #define SLAM_EKF_ABI_VERSION 3
 #define EKF_MAX_LINES 64 /* lines per scan per instance; main.cpp:99 reserves 20 */
 
@@ -442,6 +443,63 @@ int ekf_resample(ekf_ctx* ctx, const int32_t* src /* [E], host */);
 /* ekf_resample with src = identity except src[dst] = from (from must keep its state: always true
  * here). EKF_ERANGE for dst or from outside [0, E); dst == from is valid and launches nothing. */
 int ekf_copy_instance(ekf_ctx* ctx, int dst, int from);
+
+/* Instance images: instances moved between contexts (the ranks of an ensemble sharded over GPUs, a
+ * file), where ekf_resample moves them inside one. The reference has one filter and no such member.
+ * An image is everything an instance owns (what ekf_resample copies) in a position-independent form:
+ *   one 16-byte padded section per item, no addresses and no ring positions inside. The landmark
+ *   buffers come in logical order (the one the scans read, then on the pipelined schedule the newest
+ *   flush's output), the pending steps' ring slots oldest first, the newest result record when nothing
+ *   is pending. Its size depends on the configuration and on the steps pending now, not on E.
+ * Export is a raw copy into images + k * bytes for instance inst[k] and fills desc[k], the image's
+ *   host-side label, which travels with it. It changes nothing in the context; the host form and the
+ *   device form give the same bytes (padding zero), and so do two exports with nothing in between.
+ * Import reads image k into slot inst[k] of a context that is congruent with the image: equal key
+ *   (the layout and every ekf_config field but device and instances), equal pending, has_step and
+ *   groups. Ranks fed in lockstep from one broadcast scan stream are congruent by construction; the
+ *   number of steps so far, the ring position, the buffer parity and the launch epoch may differ (the
+ *   import maps the sections onto the destination's own ring slots and buffers, and gives the
+ *   completion words of the source's last launch the destination's epoch). Afterwards every read entry
+ *   point returns for the slot what it returned for the exported instance at the export, bit for bit
+ *   (ekf_read_results: the source's record and status bits), and fed the same scans the slot produces
+ *   the source's bits from then on, under every precision, arithmetic, schedule and option: the
+ *   contract of ekf_resample across contexts. No other instance receives a byte.
+ * Neither call drains, flushes, adds a step or moves the schedule; an instance never imported over is
+ *   bit-identical to the same instance of a context that never made a call, also on the split
+ *   arithmetics.
+ * Host forms: images and desc in host memory; synchronous (one copy per section, one wait, no kernel).
+ * Device forms: d_images in device memory, 4-byte aligned (16 for full speed); one launch,
+ *   asynchronous on the context stream, behind every scan enqueued so far; inst and desc are host
+ *   arrays, read or written before the call returns. The device forms order nothing between two
+ *   contexts: the caller orders the import after the export, with one stream shared through
+ *   ekf_set_stream (set before the first step: it drains) or with ekf_sync on the exporting context
+ *   (which drains it: on the split arithmetics that changes its instances' bits).
+ * Errors: EKF_EINVAL for a NULL context, list, buffer or descriptor, a partitioned context, a call
+ *   between ekf_predict and ekf_update, an import list with a duplicate slot, and an import of a
+ *   descriptor that is not congruent or whose magic, version or bytes are wrong; EKF_ERANGE for K < 0,
+ *   K > E or an entry outside [0, E). K == 0 is valid and launches nothing; an export list may repeat
+ *   an instance. A refused call leaves every byte as it was. */
+typedef struct ekf_image_desc {
+    uint32_t magic, version; /* layout version of the image */
+    uint64_t key;            /* what two contexts must share */
+    uint64_t bytes;          /* bytes of the image (a multiple of 16) */
+    int32_t pending;         /* steps of the open flush group inside */
+    int32_t has_step;        /* the source had run at least one step (a result record is inside) */
+    uint32_t epoch;          /* the source's launch epoch, for its completion words */
+    int32_t groups;          /* association workgroups of the source's last launch */
+    int32_t storage_exp;     /* the source's host-mirrored storage exponent */
+    int32_t reserved[5];
+} ekf_image_desc;
+/* bytes of one instance's image as the context stands now (0 for NULL or a partitioned context) */
+size_t ekf_instance_image_bytes(const ekf_ctx* ctx);
+int ekf_export_instances(ekf_ctx* ctx, const int32_t* inst /* [K], host */, int K, void* images /* K * bytes, host */,
+                         ekf_image_desc* desc /* [K], host */);
+int ekf_import_instances(ekf_ctx* ctx, const int32_t* inst /* [K], host */, int K, const void* images /* host */,
+                         const ekf_image_desc* desc /* [K], host */);
+int ekf_export_instances_device(ekf_ctx* ctx, const int32_t* inst /* [K], host */, int K, void* d_images /* device */,
+                                ekf_image_desc* desc /* [K], host */);
+int ekf_import_instances_device(ekf_ctx* ctx, const int32_t* inst /* [K], host */, int K, const void* d_images /* device */,
+                                const ekf_image_desc* desc /* [K], host */);
 
 /* One instance with its landmark block partitioned over ranks, for maps
  * whose packed P should not (or cannot) live on one GPU. No reference member maps to these: they

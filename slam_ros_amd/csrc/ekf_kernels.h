@@ -369,6 +369,10 @@ size_t joint_lds_bytes(int max_lines);   // dynamic LDS of the joint kernel (the
 // (ekf_resample_plan.h, device-readable), grid-strided over at most 32 workgroups per CU
 struct CopySeg;
 hipError_t launch_resample(const CopySeg* table, int nseg, int ncu, hipStream_t st);
+// the device forms of ekf_export_instances / ekf_import_instances (unit_image.hip): the table of
+// ekf_image_plan.h, dealt the same way; dst_epoch: the importing context's launch epoch, which the
+// re-tag pieces give the completion words
+hipError_t launch_image(const CopySeg* table, int nseg, unsigned dst_epoch, int ncu, hipStream_t st);
 
 hipError_t launch_scan(const ScanParams& p, int precision, hipStream_t st);
 int scan_blocks_per_cu(int precision);

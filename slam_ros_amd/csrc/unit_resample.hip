@@ -9,12 +9,11 @@
 // odd, the scalars) take the same body at that width. Plain stores: the next reader is another
 // kernel, on any XCD.
 #include "ekf_kernels.h"
+#include "ekf_copy_piece.h"
 #include "ekf_resample_plan.h"
 
 namespace ekf {
 
-constexpr int RS_THREADS = 256;
-constexpr int RS_INFLIGHT = 4;
 // grid cap, workgroups per CU: 8 are resident (four waves each); the entries are dealt statically, so
 // a grid of only the resident workgroups leaves the slowest of them a tail, and a grid four times
 // that lets the dispatcher hand out the rest as workgroups retire (measured 8 / 16 / 32)
@@ -22,33 +21,7 @@ constexpr int RS_INFLIGHT = 4;
 #define EKF_RS_BLOCKS_PER_CU 32
 #endif
 constexpr int RS_BLOCKS_PER_CU = EKF_RS_BLOCKS_PER_CU;
-static_assert(RS_INFLIGHT == 4, "copy_piece names its four values");
 static_assert(RS_CHUNK == RS_THREADS * 16 * RS_INFLIGHT, "a 16-byte-class chunk is one round of loads");
-
-// (the compiler's own vector types: the accesses carry an address space)
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-template <typename V>
-__device__ __forceinline__ void copy_piece(uint64_t src, uint64_t dst, unsigned bytes, unsigned tid)
-{
-    // (addresses from integers: named global, or the accesses are flat and count on lgkmcnt with the
-    // table's scalar loads)
-    const __attribute__((address_space(1))) V* s = reinterpret_cast<const __attribute__((address_space(1))) V*>(src);
-    __attribute__((address_space(1))) V* d = reinterpret_cast<__attribute__((address_space(1))) V*>(dst);
-    const unsigned nv = bytes / (unsigned)sizeof(V);
-    unsigned i = tid;
-    // whole rounds: four loads in flight per lane, then their stores (named values: an indexed
-    // array here is promoted to LDS)
-    for (; i + 3 * RS_THREADS < nv; i += RS_INFLIGHT * RS_THREADS) {
-        const V a = s[i], b = s[i + RS_THREADS], c = s[i + 2 * RS_THREADS], e = s[i + 3 * RS_THREADS];
-        d[i] = a;
-        d[i + RS_THREADS] = b;
-        d[i + 2 * RS_THREADS] = c;
-        d[i + 3 * RS_THREADS] = e;
-    }
-    for (; i < nv; i += RS_THREADS) d[i] = s[i];
-}
 
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const CopySeg* __restrict__ table, int nseg)
 {

@@ -45,6 +45,8 @@ EXPORTED = [
     "ekf_query_joint", "ekf_query_marginals", "ekf_query_joint_device",
     "ekf_gate_lines", "ekf_gate_lines_device", "ekf_gate_joint", "ekf_gate_joint_device",
     "ekf_resample", "ekf_copy_instance",
+    "ekf_instance_image_bytes", "ekf_export_instances", "ekf_import_instances",
+    "ekf_export_instances_device", "ekf_import_instances_device",
     "ekf_landmark_block_bytes",
     "ekf_state_dim", "ekf_profile_enable", "ekf_profile_read", "ekf_profile_flushes",
     "ekf_flush_kernel_name", "ekf_debug_scan_stamps", "ekf_debug_result_words",
@@ -99,6 +101,19 @@ class EkfJointHit(ctypes.Structure):
 
 
 ekf_joint_hit = EkfJointHit   # (the C name)
+
+
+class EkfImageDesc(ctypes.Structure):
+    """ekf_image_desc (slam_ekf.h): the host-side label of one instance image; travels with it."""
+    _fields_ = [
+        ("magic", ctypes.c_uint32), ("version", ctypes.c_uint32), ("key", ctypes.c_uint64),
+        ("bytes", ctypes.c_uint64), ("pending", ctypes.c_int32), ("has_step", ctypes.c_int32),
+        ("epoch", ctypes.c_uint32), ("groups", ctypes.c_int32), ("storage_exp", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 5),
+    ]
+
+
+ekf_image_desc = EkfImageDesc   # (the C name)
 
 
 class EkfError(RuntimeError):
@@ -161,6 +176,11 @@ def load_library(path: str = ""):
         "ekf_gate_joint_device": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, vp, vp]),
         "ekf_resample": (ctypes.c_int, [vp, ip]),
         "ekf_copy_instance": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
+        "ekf_instance_image_bytes": (sz, [vp]),
+        "ekf_export_instances": (ctypes.c_int, [vp, ip, ctypes.c_int, vp, vp]),
+        "ekf_import_instances": (ctypes.c_int, [vp, ip, ctypes.c_int, vp, vp]),
+        "ekf_export_instances_device": (ctypes.c_int, [vp, ip, ctypes.c_int, vp, vp]),
+        "ekf_import_instances_device": (ctypes.c_int, [vp, ip, ctypes.c_int, vp, vp]),
         "ekf_landmark_block_bytes": (sz, [vp]),
         "ekf_state_dim": (ctypes.c_int, [vp]),
         "ekf_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
@@ -517,6 +537,75 @@ class Ensemble:
     def copy_instance(self, dst: int, src: int):
         """Instance dst becomes a copy of instance src (ekf_copy_instance): forks a hypothesis."""
         _check(self._lib.ekf_copy_instance(self._h, int(dst), int(src)), "ekf_copy_instance")
+
+    def instance_image_bytes(self) -> int:
+        """Bytes of one instance's image as the context stands now (ekf_instance_image_bytes): it grows
+        with the steps pending in the open flush group."""
+        return int(self._lib.ekf_instance_image_bytes(self._h))
+
+    @staticmethod
+    def _inst_list(inst):
+        ia = np.ascontiguousarray(np.asarray(inst, dtype=np.int32).reshape(-1))
+        # (an empty list still hands the library a pointer)
+        return ia, (ia if ia.size else np.zeros(1, dtype=np.int32)).ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+    @staticmethod
+    def _desc_array(descs, K: int):
+        arr = (EkfImageDesc * max(K, 1))()
+        if len(descs) != K:
+            raise ValueError(f"import_instances: {len(descs)} descriptors for {K} instances")
+        for k, d in enumerate(descs):
+            ctypes.memmove(ctypes.byref(arr[k]), ctypes.byref(d), ctypes.sizeof(EkfImageDesc))
+        return arr
+
+    def export_instances(self, inst):
+        """Images of the instances `inst` in host memory (slam_ekf.h ekf_export_instances): (descs,
+        images) with images a uint8 array [K, bytes]. A raw copy of everything the instances own, the
+        pending steps included; nothing in the context changes, nothing drains. Synchronous."""
+        ia, ip = self._inst_list(inst)
+        K = int(ia.size)
+        images = np.zeros((K, self.instance_image_bytes()), dtype=np.uint8)
+        descs = (EkfImageDesc * max(K, 1))()
+        buf = images if images.size else np.zeros(16, dtype=np.uint8)
+        _check(self._lib.ekf_export_instances(self._h, ip, K, buf.ctypes.data_as(ctypes.c_void_p), ctypes.byref(descs)),
+               "ekf_export_instances")
+        return [descs[k] for k in range(K)], images
+
+    def import_instances(self, inst, images, descs):
+        """Slot inst[k] takes image k (ekf_import_instances): afterwards it reads, and from then on
+        computes, bit for bit as the exported instance did. The context must be congruent with the
+        descriptors (same configuration, as many steps pending); its other instances are untouched and
+        nothing drains. Synchronous."""
+        ia, ip = self._inst_list(inst)
+        K = int(ia.size)
+        im = np.ascontiguousarray(np.asarray(images, dtype=np.uint8).reshape(K, -1) if K else np.zeros((0, 16), dtype=np.uint8))
+        arr = self._desc_array(list(descs), K)
+        if any(int(arr[k].bytes) != im.shape[1] for k in range(K)):   # (the library reads desc.bytes per image)
+            raise ValueError("import_instances: the images are not of their descriptors' size")
+        buf = im if im.size else np.zeros(16, dtype=np.uint8)
+        _check(self._lib.ekf_import_instances(self._h, ip, K, buf.ctypes.data_as(ctypes.c_void_p), ctypes.byref(arr)),
+               "ekf_import_instances")
+
+    def export_instances_device(self, inst, d_images: int):
+        """The export into device memory at address d_images (K · instance_image_bytes() bytes; one
+        launch, asynchronous on the context stream): returns the descriptors. Nothing orders another
+        context's import after it: share a stream (set_stream, before the first step) or sync() first,
+        which drains."""
+        ia, ip = self._inst_list(inst)
+        K = int(ia.size)
+        descs = (EkfImageDesc * max(K, 1))()
+        _check(self._lib.ekf_export_instances_device(self._h, ip, K, ctypes.c_void_p(d_images or None), ctypes.byref(descs)),
+               "ekf_export_instances_device")
+        return [descs[k] for k in range(K)]
+
+    def import_instances_device(self, inst, d_images: int, descs):
+        """The import from device memory at address d_images (one launch, asynchronous on the context
+        stream)."""
+        ia, ip = self._inst_list(inst)
+        K = int(ia.size)
+        arr = self._desc_array(list(descs), K)
+        _check(self._lib.ekf_import_instances_device(self._h, ip, K, ctypes.c_void_p(d_images or None), ctypes.byref(arr)),
+               "ekf_import_instances_device")
 
     def ellipse(self, e: int = 0):
         axii = (ctypes.c_float * 2)()
