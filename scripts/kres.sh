@@ -5,7 +5,8 @@ PAT=${2:-scan_kernel}
 T=$(mktemp -d)
 cp $LIB $T/lib.so
 (cd $T && /opt/rocm/lib/llvm/bin/llvm-objdump --offloading lib.so > /dev/null)
-/opt/rocm/lib/llvm/bin/llvm-readelf --notes $T/lib.so.0.hipv4-amdgcn-amd-amdhsa--gfx950 | \
+# (one code object per compilation unit that holds kernels: all of them)
+/opt/rocm/lib/llvm/bin/llvm-readelf --notes $T/lib.so.*.hipv4-amdgcn-amd-amdhsa--gfx950 | \
   python3 -c "
 import sys, re
 pat = re.compile(sys.argv[1]); cur = {}; out = []

@@ -83,11 +83,13 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-mllvm", "-amdgpu-mfma-vgpr-for
 # the query unit ekf_device.h alone, the gate and joint units ekf_gate.h, the resample and image units only
 # their tables' headers and the shared copy body, the others the association kernels,
 # ekf_kernels.hip, which is not compiled on its own) and defines
-# the launchers that instantiate them; they compile in parallel with ekf_api.hip.
+# the launchers that instantiate them; they compile in parallel with the host units: ekf_api.hip (the
+# context and the schedule), ekf_read.hip (queries, gate, joint gate) and ekf_copy.hip (resample, images),
+# which share ekf_ctx.h.
 UNITS = ["unit_flush_f16x3.hip", "unit_flush_exact.hip", "unit_scan.hip", "unit_scan_nt128.hip",
          "unit_scan_nt64.hip", "unit_flush_2x4.hip", "unit_flush_bf16x6.hip", "unit_shard_pack.hip",
-         "unit_flush_quad.hip", "unit_query.hip", "unit_gate.hip", "unit_joint.hip", "ekf_api.hip", "unit_resample.hip",
-         "unit_image.hip"]
+         "unit_flush_quad.hip", "unit_query.hip", "unit_gate.hip", "unit_joint.hip", "ekf_api.hip",
+         "ekf_read.hip", "ekf_copy.hip", "unit_resample.hip", "unit_image.hip"]
 
 
 def source_deps(csrc: str = CSRC) -> list[str]:

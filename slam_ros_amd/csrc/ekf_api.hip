@@ -1,4 +1,7 @@
-// ekf_api.hip — C-ABI (include/slam_ekf.h) over the gfx950 kernels (launchers: unit_*.hip).
+// ekf_api.hip — C-ABI (include/slam_ekf.h) over the gfx950 kernels (launchers: unit_*.hip): the context
+// (ekf_ctx.h), the schedule, scans and flushes, state upload / download, the partitioned instance. The
+// calls that leave the schedule as it is live beside it: ekf_read.hip (ekf_query_*, ekf_gate_lines*,
+// ekf_gate_joint*) and ekf_copy.hip (ekf_resample, ekf_copy_instance, the instance images).
 //
 // A context owns E instances' state in HBM and two HIP streams:
 //   S  association/gain kernels (scan_kernel) — all state except the landmark block — and, on
@@ -19,191 +22,17 @@
 // schedule as it is. ekf_resample copies instances onto others with their pending steps, mid-group,
 // and leaves it as it is too; ekf_export_instances / ekf_import_instances do the same between
 // contexts that stand at the same point of their flush groups.
-#include <hip/hip_runtime.h>
-
 #include <math.h>
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include <dlfcn.h>
 
 #include <algorithm>
 #include <new>
-#include <vector>
 
 #include <rccl/rccl.h>   // (types only: the library loads RCCL on first use, ekf_rccl_unique_id)
 
-#include "../../include/slam_ekf.h"
-#include "ekf_kernels.h"
-#include "ekf_resample_plan.h"
-#include "ekf_image_plan.h"
-
-using ekf::Dims;
-
-struct EvPair {
-    hipEvent_t a, b;
-};
-
-struct ekf_ctx {
-    ekf_config cfg;
-    Dims d;
-    int device;
-    hipStream_t own_stream;   // S unless the caller supplies one
-    hipStream_t stream;       // S
-    hipStream_t dstream;      // D
-    size_t elem;              // bytes per stored landmark-block element
-    size_t op_elem;           // bytes per downdate operand element (fp32 for fp16 storage)
-    size_t pll_inst;          // elements per instance (the whole packed block)
-    long long t0 = 0, t1 = 0; // tiles stored per instance [t0, t1): all, unless partitioned (ekf_shard_create)
-    size_t xinst;             // stored landmark-block elements per instance ((t1 − t0)·TILE_ELEMS)
-    size_t op_inst;           // operand elements per instance
-    std::vector<void*> dev_mem;      // every device buffer create_ctx made (dev_alloc), freed by free_all
-    std::vector<void*> pinned_mem;   // ... and every pinned host buffer (pinned_alloc)
-    void* X[2];
-    double* Rs;               // [2][E][3][n] robot strip, two copies (the association kernel reads
-    double* y;                // [2][E][n]    copy cur[e] and writes the other; the lead commits it)
-    int* cur;                 // [E] committed copy per instance (device; read back when needed)
-    double* dense = nullptr;   // n × n fp64 scratch of upload / download / rescale (allocated on first use, kept)
-    // the host queries' result buffers (ekf_query_joint / ekf_query_marginals), sized to the largest
-    // request so far and kept: device scratch, and pinned host memory the one copy lands in, with the
-    // request's landmark indices behind the results (the kernel reads them through q_host_dev)
-    double* q_dev = nullptr;
-    char* q_host = nullptr;
-    char* q_host_dev = nullptr;
-    size_t q_dev_bytes = 0, q_host_bytes = 0;
-    // ekf_gate_lines: the candidates' flag bytes [E][max_lines][N] and the waves' partial records
-    // [E][max_lines][⌈N/64⌉] (listed context memory, made on first use); predicted: ekf_predict ran and
-    // no update, localize or state write since (the committed strip is the predicted one)
-    unsigned char* g_flags = nullptr;
-    ekf::GatePart* g_part = nullptr;
-    int predicted = 0;
-    // ekf_resample and the device forms of the instance images: the copy table in pinned host memory
-    // the kernel reads (sized to the largest call so far and kept), and the event behind the last
-    // launch that reads it
-    ekf::CopySeg* rs_host = nullptr;
-    ekf::CopySeg* rs_host_dev = nullptr;
-    size_t rs_cap = 0;
-    hipEvent_t rs_ev = nullptr;
-    int rs_pending = 0;
-    // partitioned instance (ekf_shard_create): rank sh_rank of sh_world stores tile rows [sh_r0, sh_r1);
-    // the running scan's replicated state
-    int sh_rank = -1, sh_world = 0, sh_r0 = 0, sh_r1 = 0;
-    double* sh_rob = nullptr;
-    double* sh_rec = nullptr;
-    double* sh_hist = nullptr;
-    double* sh_pkg = nullptr;
-    int* sh_flags = nullptr;
-    int* sh_ctl = nullptr;
-    int sh_L = 0, sh_line = 0, sh_open = 0;   // sh_open: 1 during a scan; sh_line: the next line expected
-    int sh_diag = 0;                           // begin's exchange consumed (SH_DIAG ran) in this scan
-    ekf::Slot sh_null;        // a step that applies nothing (pads an odd partial group to the wave flush)
-    double* pose;
-    double* xpre;
-    int* saved;
-    double* D;                // [2][E][N][4] diagonal landmark blocks after the last committed step
-                              // (split-bf16 contexts: the association kernel's MFMA replay)
-    std::vector<ekf::Slot> ring;   // R per-step slots
-    double* Ust;              // fp64 gain scratch of the running scan
-    double* Vst;
-    int2* tile_rc;
-    int2* stile_rc;
-    int2* stile2_rc;
-    int nstiles2;
-    ekf::WtEntry* wt;
-    int nwt;
-    ekf::WtEntry* wt64;
-    int nwt64;
-    int* wt24;                // split-bf16 wave-tiles of 2 × 4 tiles (wr | wc << 16), panel order
-    int nwt24;
-    ekf::WtEntry* wtq;        // split-fp16 quad form: groups of 2 × 2 wave-tiles (four entries each)
-    int nwtq;
-    double* d_enc;            // the scan inputs: views of d_in, staged from h_in by one copy
-    ekf_line* d_lines;
-    int* d_nlines;
-    char* d_in;
-    char* h_in;               // pinned
-    size_t in_lines, in_nlines, in_bytes;   // byte offsets of the lines and counts, the total
-    int in_pending;           // a copy from h_in was enqueued (ev_in)
-    hipEvent_t ev_in;
-    void* rccl_comm;          // ekf_shard_attach_rccl: the partitioned instance's own communicator
-    double* sh_xbuf;          // ... and ekf_shard_localize's exchange buffers (device): [N][4] + flag,
-    double* sh_xcols;         // [L][N][4] + flag + stopping line
-    double* h_agree;          // pinned: the agreement pair and a flag word
-    int sh_dirty;             // a failed scan left nonzero flag words
-    int* h_res;
-    double* h_pose;
-    // the synchronous calls' result mirror (ScanParams::res_host): pinned, written by the scan's
-    // lead; h_r33 the robot block, h_ep the epoch of each instance's last mirrored commit
-    double* h_r33;
-    unsigned* h_ep;
-    int* hd_res;              // (their device pointers)
-    double* hd_pose;
-    double* hd_r33;
-    unsigned* hd_ep;
-    int mirror_on;            // the association launch being enqueued writes the mirror
-    unsigned mirror_epoch;    // scan_epoch of the mirrored robot blocks (0: none valid)
-    int dd_grid;
-    int dd_per_cu;            // flush workgroups per CU of the grid-strided forms (EKF_OPT_FLUSH_BLOCKS_PER_CU)
-    int dd_variant;           // f32 flush kernel form (EKF_OPT_FLUSH_FORM)
-    int ncu;
-    int G;                    // association workgroups per instance
-    int mbw;                  // mailbox words per workgroup slot
-    int spec;                 // speculative association (EKF_OPT_SPECULATE)
-    int spin_log2;            // spin bound of the association kernel's waits (EKF_OPT_SPIN_LOG2)
-    int test_drop;            // test hook (EKF_OPT_TEST_DROP_WG = e + 1): instance e's last workgroup never runs
-    int test_verdict;         // test hook (EKF_OPT_TEST_VERDICT_TIMEOUT = e + 1)
-    int mfrep_opt;            // EKF_OPT_MFMA_REPLAY
-    int active_flush;         // EKF_OPT_ACTIVE_FLUSH
-    int mfrep;                // split-bf16 contexts: MFMA replay of pending steps (bf && mfrep_opt)
-    int scan_batch;           // instances per association launch (co-residency bound), 192 wide
-    int resident;             // association workgroups the device holds at once
-    int nt_opt;               // EKF_OPT_SCAN_THREADS
-    int Gmax;                 // workgroups per instance at the narrowest width (mailbox, sync words)
-    int last_G;               // workgroups per instance of the last association launch
-    unsigned scan_epoch;      // association launches so far (mailbox tags)
-    double* mbox;
-    int* sync;
-    int sync_stride;
-    unsigned long long* dbg;  // association-kernel phase timers (EKF_OPT_SCAN_STAMPS = 1, else null)
-    int* pexp;                // [E] fp16 storage exponents (device), host copy below
-    void* sink;               // scratch tile for the wave flushes (DowndateParams::sink)
-    void* ops_u;              // operand rows of every ring slot (U), slot_bytes apart
-    void* ops_v;              // ... (V)
-    long long slot_bytes;
-    void* ops_b;              // split-plane arithmetics: the planes of V of every ring slot (else null)
-    long long bslot_bytes;
-    bool bf;                  // a split-plane flush applies (arith, fp32 operands, symmetric R, kmax 16)
-    int pmode;                // its plane arithmetic: 1 EKF_ARITH_BF16X6, 2 EKF_ARITH_F16X3 (0: none)
-    int* psig;                // [E] EKF_ARITH_F16X3 plane exponent σ (device; the association kernel's
-    double* pvmax;            // [E] lead lowers it when a new landmark raises the largest variance)
-    std::vector<int> pexp_h;
-    // flush scheduling (see the top of this file)
-    int T;                    // flush interval
-    long long nsteps;         // update steps enqueued
-    long long unflushed0;     // first step not covered by an enqueued flush
-    long long pend0;          // first step not contained in X[base]
-    int base;                 // buffer the association kernels read
-    int last_out;             // buffer the newest enqueued flush writes (materialised after drain)
-    long long nflush;
-    hipEvent_t ev_scan;       // recorded on S after each update scan
-    hipEvent_t ev_flush[2];   // recorded on D after flush f (f & 1)
-    hipEvent_t ev_base;       // event guarding X[base] and the ring (nullptr: none pending)
-    // profiling
-    int prof;
-    std::vector<EvPair> ev[3];   // scan, downdate, patch
-    std::vector<int> ev_nsteps;  // steps applied by each timed flush (ev[1])
-    std::vector<EvPair> pool;
-};
-
-#define HIP_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) {                                                             \
-            fprintf(stderr, "slam_ekf: %s failed: %s\n", #expr, hipGetErrorString(_e));     \
-            return EKF_EDEVICE;                                                             \
-        }                                                                                   \
-    } while (0)
+#include "ekf_ctx.h"
 
 extern "C" {
 
@@ -240,7 +69,7 @@ int ekf_abi_version(void) { return SLAM_EKF_ABI_VERSION; }
 
 // The context's memory: every buffer create_ctx makes goes through these two and is freed from the
 // lists (free_all); only the buffers made or remade later are freed by name
-static bool dev_alloc(ekf_ctx* c, void** p, size_t bytes)
+bool dev_alloc(ekf_ctx* c, void** p, size_t bytes)
 {
     if (hipMalloc(p, bytes) != hipSuccess) return false;
     c->dev_mem.push_back(*p);
@@ -252,6 +81,28 @@ static bool pinned_alloc(ekf_ctx* c, void** p, size_t bytes)
     if (hipHostMalloc(p, bytes) != hipSuccess) return false;
     c->pinned_mem.push_back(*p);
     return true;
+}
+
+static void pinned_release(PinnedBuf& b)
+{
+    if (b.host) (void)hipHostFree(b.host);
+    b = PinnedBuf();
+}
+
+int pinned_reserve(PinnedBuf& b, size_t bytes)
+{
+    if (bytes <= b.cap) return EKF_OK;
+    pinned_release(b);
+    if (hipHostMalloc((void**)&b.host, bytes) != hipSuccess) {
+        b.host = nullptr;
+        return EKF_ENOMEM;
+    }
+    if (hipHostGetDevicePointer((void**)&b.dev, b.host, 0) != hipSuccess) {
+        pinned_release(b);
+        return EKF_EDEVICE;
+    }
+    b.cap = bytes;
+    return EKF_OK;
 }
 
 // A host-built table (ekf_tables.h) into device memory of its own; *count: its entries
@@ -272,8 +123,8 @@ static void free_all(ekf_ctx* c)
     for (void* p : c->dev_mem) (void)hipFree(p);
     for (void* p : {(void*)c->dbg, (void*)c->dense, (void*)c->q_dev, (void*)c->sh_xbuf, (void*)c->sh_xcols})
         (void)hipFree(p);   // (or null)
-    if (c->q_host) (void)hipHostFree(c->q_host);
-    if (c->rs_host) (void)hipHostFree(c->rs_host);
+    pinned_release(c->q_pin);
+    pinned_release(c->rs_pin);
     if (c->rs_ev) (void)hipEventDestroy(c->rs_ev);
     for (void* p : c->pinned_mem) (void)hipHostFree(p);
     if (c->h_agree) (void)hipHostFree(c->h_agree);
@@ -317,6 +168,15 @@ static int begin_state_write(ekf_ctx* c)
     return drain(c);
 }
 
+int end_read(ekf_ctx* c)
+{
+    // Pipelined schedule: the next flush (a drain's, or the group's) writes X[base] on D, ordered
+    // only after ev_scan, which the last scan recorded before this work was enqueued. ev_scan is
+    // recorded again here, behind the work on S, so that flush also waits for it.
+    if (c->cfg.pipeline) HIP_TRY(hipEventRecord(c->ev_scan, c->stream));
+    return EKF_OK;
+}
+
 static inline int cur_buf(const ekf_ctx* c) { return c->last_out; }
 
 // instance e's stored tiles in buffer buf; and the kernels' view of instance 0, in which tile t sits
@@ -325,7 +185,7 @@ static inline char* xinst_ptr(const ekf_ctx* c, int buf, int e)
 {
     return (char*)c->X[buf] + (size_t)e * c->xinst * c->elem;
 }
-static inline void* xview(const ekf_ctx* c, int buf)
+void* xview(const ekf_ctx* c, int buf)
 {
     return (char*)c->X[buf] - (ptrdiff_t)c->t0 * ekf::TILE_ELEMS * (ptrdiff_t)c->elem;
 }
@@ -805,7 +665,7 @@ static void prof_end(ekf_ctx* c, EvPair* pr, hipStream_t st)
 // Symmetric fp32 operands (sym_factor: every EKF_R_INTENDED fp32 / fp16 context; U = −2^x·V
 // exactly): the association kernel stores the V rows only and every reader of U rows scales them
 // (ScanParams / DowndateParams::usym). The partitioned instance stores both.
-static int usym_of(const ekf_ctx* c)
+int usym_of(const ekf_ctx* c)
 {
     return c->sh_world == 0 && c->cfg.precision != EKF_PREC_F64 && c->cfg.r_mode == EKF_R_INTENDED;
 }
@@ -892,7 +752,7 @@ static hipError_t launch_scans(ekf_ctx* c, ekf::ScanParams sp)
     return err;
 }
 
-static const ekf::Slot& slot_of(const ekf_ctx* c, long long k)
+const ekf::Slot& slot_of(const ekf_ctx* c, long long k)
 {
     return c->ring[(size_t)(k % (long long)c->ring.size())];
 }
@@ -1533,656 +1393,6 @@ extern "C" int ekf_get_ellipse(ekf_ctx* c, int e, float axii[2], float* angle)
     if (rc) return -rc;
     const double P22[4] = {P33[0], P33[1], P33[3], P33[4]};
     return gsl_ellipse_2x2(P22, axii, angle);
-}
-
-// ---- covariance queries without a drain (slam_ekf.h ekf_query_*; kernel: unit_query.hip) ----
-// The query kernel takes the view the next association kernel would take in enqueue(): X[base] once
-// the event guarding it has passed, the steps [pend0, nsteps) applied on read, the committed copy
-// of the strip and the mean. It runs on S after every scan enqueued so far and changes nothing of
-// the schedule: no flush, no step, no epoch.
-// (ekf_gate_lines takes the same view: begin_read / end_read are the hazard handling of both.)
-template <typename P>   // QueryParams or GateParams: the view's fields
-static int begin_read(ekf_ctx* c, P& qp)
-{
-    if (c->ev_base) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_base, 0));
-    const int np = (int)(c->nsteps - c->pend0);
-    if (np > ekf::PMAX) return EKF_EINVAL;   // unreachable: T <= 24
-    qp.d = c->d;
-    qp.Etot = c->cfg.instances;
-    qp.usym = usym_of(c);
-    qp.bf = c->pmode;
-    qp.npend = np;
-    qp.Pread = xview(c, c->base);
-    qp.Rs = c->Rs;
-    qp.y = c->y;
-    qp.live = c->cur;
-    qp.pexp = c->pexp;
-    for (int q = 0; q < np; q++) qp.pend[q] = slot_of(c, c->pend0 + q);
-    return EKF_OK;
-}
-
-static int end_read(ekf_ctx* c)
-{
-    // Pipelined schedule: the next flush (a drain's, or the group's) writes X[base] on D, ordered
-    // only after ev_scan, which the last scan recorded before this read was enqueued. ev_scan is
-    // recorded again here, behind the read on S, so that flush also waits for the read.
-    if (c->cfg.pipeline) HIP_TRY(hipEventRecord(c->ev_scan, c->stream));
-    return EKF_OK;
-}
-
-static int enqueue_query(ekf_ctx* c, ekf::QueryParams& qp)
-{
-    const int rc = begin_read(c, qp);
-    if (rc) return rc;
-    HIP_TRY(ekf::launch_query(qp, c->cfg.precision, c->stream));
-    return end_read(c);
-}
-
-// The host forms' buffers for a request of `bytes` result bytes and `tail` bytes of inputs behind them
-// in the pinned buffer (the queries' indices; the gate's lines and encoder pose)
-static int query_buffers(ekf_ctx* c, size_t bytes, size_t tail)
-{
-    if (bytes > c->q_dev_bytes) {
-        if (c->q_dev) (void)hipFree(c->q_dev);
-        c->q_dev = nullptr;
-        c->q_dev_bytes = 0;
-        if (hipMalloc((void**)&c->q_dev, bytes) != hipSuccess) {
-            c->q_dev = nullptr;
-            return EKF_ENOMEM;
-        }
-        c->q_dev_bytes = bytes;
-    }
-    const size_t hb = bytes + tail;
-    if (hb > c->q_host_bytes) {
-        if (c->q_host) (void)hipHostFree(c->q_host);
-        c->q_host = c->q_host_dev = nullptr;
-        c->q_host_bytes = 0;
-        if (hipHostMalloc((void**)&c->q_host, hb) != hipSuccess) {
-            c->q_host = nullptr;
-            return EKF_ENOMEM;
-        }
-        if (hipHostGetDevicePointer((void**)&c->q_host_dev, c->q_host, 0) != hipSuccess) {
-            (void)hipHostFree(c->q_host);
-            c->q_host = c->q_host_dev = nullptr;
-            return EKF_EDEVICE;
-        }
-        c->q_host_bytes = hb;
-    }
-    return EKF_OK;
-}
-
-// Argument checks shared by the host forms (before any HIP call)
-static int query_check(const ekf_ctx* c, int e, const int32_t* landmarks, int K, bool need_list)
-{
-    if (!c || c->sh_world > 0) return EKF_EINVAL;
-    if (e < 0 || e >= c->cfg.instances || K < 0 || K > c->d.N) return EKF_ERANGE;
-    if (need_list && K > 0 && !landmarks) return EKF_EINVAL;
-    if (landmarks)
-        for (int k = 0; k < K; k++)
-            if (landmarks[k] < 0 || landmarks[k] >= c->d.N) return EKF_ERANGE;
-    return EKF_OK;
-}
-
-// One kernel, one copy (into the pinned buffer), one wait; the results then leave by memcpy
-// (after query_buffers for this request)
-static int run_host_query(ekf_ctx* c, ekf::QueryParams& qp, const int32_t* landmarks, size_t bytes)
-{
-    if (landmarks) {
-        memcpy(c->q_host + bytes, landmarks, sizeof(int32_t) * (size_t)qp.K);
-        qp.landmarks = reinterpret_cast<const int32_t*>(c->q_host_dev + bytes);
-    }
-    const int rc = enqueue_query(c, qp);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->q_host, c->q_dev, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return EKF_OK;
-}
-
-extern "C" int ekf_query_joint(ekf_ctx* c, int e, const int32_t* landmarks, int K, double* cov, double* mean)
-{
-    int rc = query_check(c, e, landmarks, K, true);
-    if (rc) return rc;
-    if (!cov && !mean) return EKF_OK;
-    const size_t nq = 3 + 2 * (size_t)K;
-    const size_t ncov = cov ? nq * nq : 0;
-    ekf::QueryParams qp;
-    memset(&qp, 0, sizeof(qp));
-    qp.mode = ekf::QUERY_JOINT;
-    qp.E = 1;
-    qp.e0 = e;
-    qp.K = K;
-    rc = query_buffers(c, sizeof(double) * (ncov + nq), sizeof(int32_t) * (size_t)K);
-    if (rc) return rc;
-    qp.cov = cov ? c->q_dev : nullptr;
-    qp.mean = c->q_dev + ncov;
-    rc = run_host_query(c, qp, landmarks, sizeof(double) * (ncov + nq));
-    if (rc) return rc;
-    const double* h = reinterpret_cast<const double*>(c->q_host);
-    if (cov) memcpy(cov, h, sizeof(double) * ncov);
-    if (mean) memcpy(mean, h + ncov, sizeof(double) * nq);
-    return EKF_OK;
-}
-
-extern "C" int ekf_query_marginals(ekf_ctx* c, int e, const int32_t* landmarks, int K, double* blocks,
-                                   double* cross, double* mean)
-{
-    int rc = query_check(c, e, landmarks, K, false);
-    if (rc) return rc;
-    if (K == 0 || (!blocks && !cross && !mean)) return EKF_OK;
-    const size_t k = (size_t)K;
-    ekf::QueryParams qp;
-    memset(&qp, 0, sizeof(qp));
-    qp.mode = ekf::QUERY_MARGINALS;
-    qp.E = 1;
-    qp.e0 = e;
-    qp.K = K;
-    rc = query_buffers(c, sizeof(double) * 12 * k, landmarks ? sizeof(int32_t) * k : 0);
-    if (rc) return rc;
-    qp.blocks = c->q_dev;
-    qp.cross = c->q_dev + 4 * k;
-    qp.mean = c->q_dev + 10 * k;
-    rc = run_host_query(c, qp, landmarks, sizeof(double) * 12 * k);
-    if (rc) return rc;
-    const double* h = reinterpret_cast<const double*>(c->q_host);
-    if (blocks) memcpy(blocks, h, sizeof(double) * 4 * k);
-    if (cross) memcpy(cross, h + 4 * k, sizeof(double) * 6 * k);
-    if (mean) memcpy(mean, h + 10 * k, sizeof(double) * 2 * k);
-    return EKF_OK;
-}
-
-extern "C" int ekf_query_joint_device(ekf_ctx* c, const int32_t* d_landmarks, int K, double* d_cov, double* d_mean)
-{
-    if (!c || c->sh_world > 0) return EKF_EINVAL;
-    if (K < 0 || K > c->d.N) return EKF_ERANGE;
-    if (K > 0 && !d_landmarks) return EKF_EINVAL;
-    if (!d_cov && !d_mean) return EKF_OK;
-    ekf::QueryParams qp;
-    memset(&qp, 0, sizeof(qp));
-    qp.mode = ekf::QUERY_JOINT;
-    qp.E = c->cfg.instances;
-    qp.e0 = 0;
-    qp.K = K;
-    qp.landmarks = K > 0 ? d_landmarks : nullptr;
-    qp.cov = d_cov;
-    qp.mean = d_mean;
-    return enqueue_query(c, qp);
-}
-
-// ---- trial lines gated against the map (slam_ekf.h ekf_gate_lines; kernels: unit_gate.hip) ----
-// The view and the hazard handling of the queries (begin_read / end_read), the committed pose, and
-// two launches on S: nothing of the schedule or the state changes.
-static int enqueue_gate(ekf_ctx* c, ekf::GateParams& gp)
-{
-    const size_t rows = (size_t)c->cfg.instances * c->d.max_lines;
-    const int nw = (c->d.N + 63) / 64;
-    if (!c->g_flags) {
-        void* fl = nullptr;
-        void* pt = nullptr;
-        if (!dev_alloc(c, &fl, rows * c->d.N) || !dev_alloc(c, &pt, rows * nw * sizeof(ekf::GatePart)))
-            return EKF_ENOMEM;   // (listed either way: free_all releases what was made)
-        c->g_flags = (unsigned char*)fl;
-        c->g_part = (ekf::GatePart*)pt;
-    }
-    const int rc = begin_read(c, gp);
-    if (rc) return rc;
-    gp.pose = c->pose;
-    gp.xpre = c->xpre;
-    gp.saved = c->saved;
-    gp.use_xpre = c->predicted;
-    gp.r_mode = c->cfg.r_mode;
-    gp.nw = nw;
-    gp.gate = c->cfg.mahalanobis;
-    gp.enc_noise = c->cfg.encoder_noise;
-    gp.flags = c->g_flags;
-    gp.part = c->g_part;
-    HIP_TRY(ekf::launch_gate(gp, c->cfg.precision, c->stream));
-    return end_read(c);
-}
-
-extern "C" int ekf_gate_lines(ekf_ctx* c, int e, const double enc[3], const ekf_line* lines, int L,
-                              ekf_gate_hit* hits, double* d2)
-{
-    if (!c || c->sh_world > 0) return EKF_EINVAL;
-    if (e < 0 || e >= c->cfg.instances || L < 0 || L > c->d.max_lines) return EKF_ERANGE;
-    if ((L > 0 && !lines) || !hits) return EKF_EINVAL;
-    if (enc && c->predicted) return EKF_EINVAL;   // the committed strip is already the predicted one
-    if (L == 0) return EKF_OK;
-    // device scratch [hits | d2], the pinned buffer [hits | d2 | lines | enc] (inputs behind the results)
-    const size_t nh = sizeof(ekf_gate_hit) * (size_t)L;
-    const size_t nd = d2 ? sizeof(double) * (size_t)L * c->d.N : 0;
-    const size_t nl = sizeof(ekf_line) * (size_t)L;
-    int rc = query_buffers(c, nh + nd, nl + 3 * sizeof(double));
-    if (rc) return rc;
-    memcpy(c->q_host + nh + nd, lines, nl);
-    if (enc) memcpy(c->q_host + nh + nd + nl, enc, 3 * sizeof(double));
-    ekf::GateParams gp;
-    memset(&gp, 0, sizeof(gp));
-    gp.E = 1;
-    gp.e0 = e;
-    gp.L = L;
-    gp.lines = reinterpret_cast<const ekf_line*>(c->q_host_dev + nh + nd);
-    gp.enc = enc ? reinterpret_cast<const double*>(c->q_host_dev + nh + nd + nl) : nullptr;
-    char* dev = reinterpret_cast<char*>(c->q_dev);
-    gp.hits = reinterpret_cast<ekf_gate_hit*>(dev);
-    gp.d2 = d2 ? reinterpret_cast<double*>(dev + nh) : nullptr;
-    rc = enqueue_gate(c, gp);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->q_host, c->q_dev, nh + nd, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    memcpy(hits, c->q_host, nh);
-    if (d2) memcpy(d2, c->q_host + nh, nd);
-    return EKF_OK;
-}
-
-extern "C" int ekf_gate_lines_device(ekf_ctx* c, const double* d_enc, const ekf_line* d_lines,
-                                     const int32_t* d_nlines, ekf_gate_hit* d_hits, double* d_d2)
-{
-    if (!c || c->sh_world > 0 || !d_lines || !d_nlines || !d_hits) return EKF_EINVAL;
-    if (d_enc && c->predicted) return EKF_EINVAL;
-    ekf::GateParams gp;
-    memset(&gp, 0, sizeof(gp));
-    gp.E = c->cfg.instances;
-    gp.e0 = 0;
-    gp.L = 0;
-    gp.enc = d_enc;
-    gp.lines = d_lines;
-    gp.nlines = d_nlines;
-    gp.hits = d_hits;
-    gp.d2 = d_d2;
-    return enqueue_gate(c, gp);
-}
-
-// ---- joint compatibility of hypotheses (slam_ekf.h ekf_gate_joint; kernel: unit_joint.hip) ----
-// The gate's view and hazard handling, one launch on S; the kernel's only scratch is its LDS.
-static int enqueue_joint(ekf_ctx* c, ekf::JointParams& jp)
-{
-    const int rc = begin_read(c, jp);
-    if (rc) return rc;
-    jp.pose = c->pose;
-    jp.xpre = c->xpre;
-    jp.saved = c->saved;
-    jp.use_xpre = c->predicted;
-    jp.r_mode = c->cfg.r_mode;
-    jp.gate = c->cfg.mahalanobis;
-    jp.enc_noise = c->cfg.encoder_noise;
-    HIP_TRY(ekf::launch_joint(jp, c->cfg.precision, c->stream));
-    return end_read(c);
-}
-
-extern "C" int ekf_gate_joint(ekf_ctx* c, int e, const double enc[3], const ekf_line* lines, int L,
-                              const int32_t* assign, int H, ekf_joint_hit* hits, double* d2_each)
-{
-    if (!c || c->sh_world > 0) return EKF_EINVAL;
-    if (e < 0 || e >= c->cfg.instances || L < 0 || L > c->d.max_lines || H < 0) return EKF_ERANGE;
-    if ((L > 0 && !lines) || (H > 0 && !hits) || (H > 0 && L > 0 && !assign)) return EKF_EINVAL;
-    if (enc && c->predicted) return EKF_EINVAL;   // the committed strip is already the predicted one
-    const size_t HL = (size_t)H * L;
-    for (size_t k = 0; k < HL; k++)
-        if (assign[k] < -1 || assign[k] >= c->d.N) return EKF_ERANGE;
-    if (H == 0) return EKF_OK;
-    if (L == 0) {   // every hypothesis is empty
-        for (int h = 0; h < H; h++) hits[h] = ekf_joint_hit{0, 0, 0.0, 0.0};
-        return EKF_OK;
-    }
-    // device scratch [hits | d2_each], the pinned buffer [hits | d2_each | lines | enc | assign]
-    const size_t nh = sizeof(ekf_joint_hit) * (size_t)H;
-    const size_t nd = d2_each ? sizeof(double) * HL : 0;
-    const size_t nl = sizeof(ekf_line) * (size_t)L;
-    const size_t na = sizeof(int32_t) * HL;
-    int rc = query_buffers(c, nh + nd, nl + 3 * sizeof(double) + na);
-    if (rc) return rc;
-    memcpy(c->q_host + nh + nd, lines, nl);
-    if (enc) memcpy(c->q_host + nh + nd + nl, enc, 3 * sizeof(double));
-    memcpy(c->q_host + nh + nd + nl + 3 * sizeof(double), assign, na);
-    ekf::JointParams jp;
-    memset(&jp, 0, sizeof(jp));
-    jp.E = 1;
-    jp.e0 = e;
-    jp.L = L;
-    jp.H = H;
-    jp.astride = L;
-    jp.lines = reinterpret_cast<const ekf_line*>(c->q_host_dev + nh + nd);
-    jp.enc = enc ? reinterpret_cast<const double*>(c->q_host_dev + nh + nd + nl) : nullptr;
-    jp.assign = reinterpret_cast<const int32_t*>(c->q_host_dev + nh + nd + nl + 3 * sizeof(double));
-    char* dev = reinterpret_cast<char*>(c->q_dev);
-    jp.hits = reinterpret_cast<ekf_joint_hit*>(dev);
-    jp.d2_each = d2_each ? reinterpret_cast<double*>(dev + nh) : nullptr;
-    rc = enqueue_joint(c, jp);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->q_host, c->q_dev, nh + nd, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    memcpy(hits, c->q_host, nh);
-    if (d2_each) memcpy(d2_each, c->q_host + nh, nd);
-    return EKF_OK;
-}
-
-extern "C" int ekf_gate_joint_device(ekf_ctx* c, const double* d_enc, const ekf_line* d_lines, const int32_t* d_nlines,
-                                     const int32_t* d_assign, int H, ekf_joint_hit* d_hits, double* d_d2_each)
-{
-    if (!c || c->sh_world > 0) return EKF_EINVAL;
-    if (H < 0) return EKF_ERANGE;
-    if (!d_lines || !d_nlines || (H > 0 && (!d_assign || !d_hits))) return EKF_EINVAL;
-    if (d_enc && c->predicted) return EKF_EINVAL;
-    if (H == 0) return EKF_OK;
-    ekf::JointParams jp;
-    memset(&jp, 0, sizeof(jp));
-    jp.E = c->cfg.instances;
-    jp.e0 = 0;
-    jp.L = 0;
-    jp.H = H;
-    jp.astride = c->d.max_lines;
-    jp.enc = d_enc;
-    jp.lines = d_lines;
-    jp.nlines = d_nlines;
-    jp.assign = d_assign;
-    jp.hits = d_hits;
-    jp.d2_each = d_d2_each;
-    return enqueue_joint(c, jp);
-}
-
-// ---- instances copied onto others (slam_ekf.h ekf_resample; kernel: unit_resample.hip) ----
-// Every per-instance slice the kernels read later goes from instance src[e] to instance e in one
-// launch on S (the table: ekf_resample_plan.h). Nothing of the schedule changes: no flush, no step,
-// no epoch, and not a byte of an instance that keeps its state.
-static ekf::ResampleLayout resample_layout(const ekf_ctx* c)
-{
-    ekf::ResampleLayout L;
-    auto addr = [](const void* p) { return (uint64_t)(uintptr_t)p; };
-    L.d = c->d;
-    L.E = c->cfg.instances;
-    L.xinst_bytes = (uint64_t)c->xinst * c->elem;
-    L.op_elem = (int)c->op_elem;
-    L.usym = usym_of(c);
-    L.npl = c->pmode == EKF_ARITH_F16X3 ? 2 : c->pmode == EKF_ARITH_BF16X6 ? 3 : 0;
-    L.res_stride = ekf::RES_STRIDE;
-    L.sync_stride = c->sync_stride;
-    // pipelined: X[in] (the scans' base) and X[out] (the newest flush's output, the next one's input)
-    L.nX = c->cfg.pipeline ? 2 : 1;
-    L.X[0] = addr(c->X[0]);
-    L.X[1] = addr(c->X[1]);
-    L.Rs = addr(c->Rs);
-    L.y = addr(c->y);
-    L.D = addr(c->D);
-    L.cur = addr(c->cur);
-    L.saved = addr(c->saved);
-    L.pexp = addr(c->pexp);
-    L.psig = addr(c->psig);
-    L.pose = addr(c->pose);
-    L.xpre = addr(c->xpre);
-    L.pvmax = addr(c->pvmax);
-    L.sync = addr(c->sync);
-    L.ops_u = addr(c->ops_u);
-    L.ops_v = addr(c->ops_v);
-    L.ops_b = addr(c->ops_b);
-    L.slot_bytes = (uint64_t)c->slot_bytes;
-    L.bslot_bytes = (uint64_t)c->bslot_bytes;
-    for (const ekf::Slot& sl : c->ring) {
-        L.patch.push_back(addr(sl.patch));
-        L.patch_diag.push_back(addr(sl.patch_diag));
-        L.res.push_back(addr(sl.res));
-    }
-    const long long R = (long long)c->ring.size();
-    for (long long k = c->pend0; k < c->nsteps; k++) L.pending.push_back((int)(k % R));
-    L.newest = c->nsteps > 0 ? (int)((c->nsteps - 1) % R) : -1;
-    return L;
-}
-
-// A copy table into the context's pinned buffer, which is rewritten only after the last launch that
-// reads it (rs_ev); the launch that follows is closed with rs_launched
-static int rs_stage(ekf_ctx* c, const std::vector<ekf::CopySeg>& table)
-{
-    if (c->rs_pending) HIP_TRY(hipEventSynchronize(c->rs_ev));
-    c->rs_pending = 0;
-    if (!c->rs_ev) HIP_TRY(hipEventCreateWithFlags(&c->rs_ev, hipEventDisableTiming));
-    if (table.size() > c->rs_cap) {
-        if (c->rs_host) (void)hipHostFree(c->rs_host);
-        c->rs_host = c->rs_host_dev = nullptr;
-        c->rs_cap = 0;
-        if (hipHostMalloc((void**)&c->rs_host, sizeof(ekf::CopySeg) * table.size()) != hipSuccess) {
-            c->rs_host = nullptr;
-            return EKF_ENOMEM;
-        }
-        if (hipHostGetDevicePointer((void**)&c->rs_host_dev, c->rs_host, 0) != hipSuccess) {
-            (void)hipHostFree(c->rs_host);
-            c->rs_host = c->rs_host_dev = nullptr;
-            return EKF_EDEVICE;
-        }
-        c->rs_cap = table.size();
-    }
-    memcpy(c->rs_host, table.data(), sizeof(ekf::CopySeg) * table.size());
-    return EKF_OK;
-}
-
-static int rs_launched(ekf_ctx* c)
-{
-    HIP_TRY(hipEventRecord(c->rs_ev, c->stream));
-    c->rs_pending = 1;
-    return EKF_OK;
-}
-
-// The hazards of a table-driven copy on S that reads or writes X[base], the ring and, pipelined,
-// X[out]: behind the event guarding base (as enqueue) and behind the newest flush on D, which reads
-// X[in] and the ring and writes X[out]
-static int rs_wait(ekf_ctx* c)
-{
-    if (c->ev_base) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_base, 0));
-    if (c->cfg.pipeline && c->nflush > 0)
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_flush[(c->nflush - 1) & 1], 0));
-    return EKF_OK;
-}
-
-extern "C" int ekf_resample(ekf_ctx* c, const int32_t* src)
-{
-    if (!c || !src || c->sh_world > 0) return EKF_EINVAL;
-    const int E = c->cfg.instances;
-    const int bad = ekf::resample_check(src, E);
-    if (bad) return bad == 2 ? EKF_ERANGE : EKF_EINVAL;
-    if (c->predicted) return EKF_EINVAL;   // the committed strip is the predicted one
-    bool any = false;
-    for (int e = 0; e < E; e++) any = any || src[e] != e;
-    if (!any) return EKF_OK;
-    const std::vector<ekf::CopySeg> table = ekf::resample_plan(ekf::resample_arrays(resample_layout(c)), E, src);
-    int rc = rs_stage(c, table);
-    if (rc) return rc;
-    rc = rs_wait(c);
-    if (rc) return rc;
-    HIP_TRY(ekf::launch_resample(c->rs_host_dev, (int)table.size(), c->ncu, c->stream));
-    rc = rs_launched(c);
-    if (rc) return rc;
-    // the next flush on D waits for the copy too (end_read)
-    if (c->cfg.pipeline) HIP_TRY(hipEventRecord(c->ev_scan, c->stream));
-    for (int e = 0; e < E; e++) c->pexp_h[e] = c->pexp_h[src[e]];   // (a source keeps its own: fixed points)
-    c->mirror_epoch = 0;   // the mirrored robot blocks are stale for the overwritten instances
-    return EKF_OK;
-}
-
-extern "C" int ekf_copy_instance(ekf_ctx* c, int dst, int from)
-{
-    if (!c || c->sh_world > 0) return EKF_EINVAL;
-    const int E = c->cfg.instances;
-    if (dst < 0 || dst >= E || from < 0 || from >= E) return EKF_ERANGE;
-    std::vector<int32_t> src((size_t)E);
-    for (int e = 0; e < E; e++) src[e] = e;
-    src[dst] = from;
-    return ekf_resample(c, src.data());
-}
-
-// ---- instance images (slam_ekf.h ekf_export_instances / ekf_import_instances; table:
-// ekf_image_plan.h; kernel of the device forms: unit_image.hip) ----
-// The arrays of ekf_resample in logical order, one instance of each as a 16-byte padded section.
-// Nothing of the schedule changes in either direction; the import maps the sections onto this
-// context's own ring slots and buffers and re-tags the completion words with its epoch.
-static std::vector<ekf::ResampleArray> image_arrays_of(const ekf_ctx* c)
-{
-    return ekf::image_arrays(resample_layout(c), c->base);
-}
-
-static uint64_t image_key_of(const ekf_ctx* c)
-{
-    const ekf_config& g = c->cfg;
-    const ekf::ImageConfig ic = {g.capacity, g.precision, g.max_lines, g.r_mode, g.reset_margin, g.pipeline ? 1 : 0,
-                                 c->T, g.arith, g.mahalanobis, g.encoder_noise};
-    return ekf::image_key(resample_layout(c), (int)c->elem, ic);
-}
-
-extern "C" size_t ekf_instance_image_bytes(const ekf_ctx* c)
-{
-    if (!c || c->sh_world > 0) return 0;
-    return (size_t)ekf::image_bytes(image_arrays_of(c));
-}
-
-// The checks both directions share; 0 or the status to return
-static int image_args(const ekf_ctx* c, const int32_t* inst, int K, const void* images, const void* desc)
-{
-    if (!c || !inst || !images || !desc || c->sh_world > 0) return EKF_EINVAL;
-    const int E = c->cfg.instances;
-    if (K < 0 || K > E) return EKF_ERANGE;
-    for (int k = 0; k < K; k++)
-        if (inst[k] < 0 || inst[k] >= E) return EKF_ERANGE;
-    if (c->predicted) return EKF_EINVAL;   // the committed strip is the predicted one
-    return EKF_OK;
-}
-
-static void image_describe(const ekf_ctx* c, const int32_t* inst, int K, uint64_t bytes, ekf_image_desc* desc)
-{
-    const uint64_t key = image_key_of(c);
-    for (int k = 0; k < K; k++) {
-        ekf_image_desc& d = desc[k];
-        memset(&d, 0, sizeof(d));
-        d.magic = ekf::IMAGE_MAGIC;
-        d.version = ekf::IMAGE_VERSION;
-        d.key = key;
-        d.bytes = bytes;
-        d.pending = (int32_t)(c->nsteps - c->pend0);
-        d.has_step = c->nsteps > 0;
-        d.epoch = c->scan_epoch;
-        d.groups = c->last_G;
-        d.storage_exp = c->pexp_h[inst[k]];
-    }
-}
-
-// import: the list names no slot twice and every descriptor is congruent with this context
-static int image_congruent(const ekf_ctx* c, const int32_t* inst, int K, uint64_t bytes, const ekf_image_desc* desc)
-{
-    std::vector<char> seen((size_t)c->cfg.instances, 0);
-    for (int k = 0; k < K; k++) {
-        if (seen[(size_t)inst[k]]) return EKF_EINVAL;
-        seen[(size_t)inst[k]] = 1;
-    }
-    const uint64_t key = image_key_of(c);
-    for (int k = 0; k < K; k++) {
-        const ekf_image_desc& d = desc[k];
-        if (d.magic != ekf::IMAGE_MAGIC || d.version != ekf::IMAGE_VERSION || d.key != key || d.bytes != bytes ||
-            d.pending != (int32_t)(c->nsteps - c->pend0) || d.has_step != (c->nsteps > 0 ? 1 : 0) ||
-            d.groups != c->last_G)
-            return EKF_EINVAL;
-    }
-    return EKF_OK;
-}
-
-// the host state an imported slot takes with its image
-static void image_adopt(ekf_ctx* c, const int32_t* inst, int K, const ekf_image_desc* desc)
-{
-    for (int k = 0; k < K; k++) c->pexp_h[(size_t)inst[k]] = desc[k].storage_exp;
-    c->mirror_epoch = 0;   // the mirrored robot blocks are stale for the slots
-}
-
-extern "C" int ekf_export_instances(ekf_ctx* c, const int32_t* inst, int K, void* images, ekf_image_desc* desc)
-{
-    int rc = image_args(c, inst, K, images, desc);
-    if (rc || K == 0) return rc;
-    const std::vector<ekf::ResampleArray> arrays = image_arrays_of(c);
-    const std::vector<ekf::ImageSection> sec = ekf::image_sections(arrays);
-    const uint64_t bytes = ekf::image_bytes(arrays);
-    rc = rs_wait(c);
-    if (rc) return rc;
-    for (int k = 0; k < K; k++)
-        for (const ekf::ImageSection& s : sec) {
-            char* q = (char*)images + (size_t)k * bytes + s.offset;
-            HIP_TRY(hipMemcpyAsync(q, (const void*)(uintptr_t)(s.base + (uint64_t)inst[k] * s.bytes), s.bytes,
-                                   hipMemcpyDeviceToHost, c->stream));
-            memset(q + s.bytes, 0, (size_t)(ekf::image_pad16(s.bytes) - s.bytes));
-        }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    image_describe(c, inst, K, bytes, desc);
-    return EKF_OK;
-}
-
-extern "C" int ekf_import_instances(ekf_ctx* c, const int32_t* inst, int K, const void* images,
-                                    const ekf_image_desc* desc)
-{
-    int rc = image_args(c, inst, K, images, desc);
-    if (rc || K == 0) return rc;
-    const std::vector<ekf::ResampleArray> arrays = image_arrays_of(c);
-    const std::vector<ekf::ImageSection> sec = ekf::image_sections(arrays);
-    const uint64_t bytes = ekf::image_bytes(arrays);
-    rc = image_congruent(c, inst, K, bytes, desc);
-    if (rc) return rc;
-    rc = rs_wait(c);
-    if (rc) return rc;
-    // the completion words on a private copy (the caller's buffer stays as exported), alive until the wait
-    const size_t sw = (size_t)c->sync_stride;
-    std::vector<uint32_t> words(sw * (size_t)K);
-    for (int k = 0; k < K; k++)
-        for (const ekf::ImageSection& s : sec) {
-            const char* p = (const char*)images + (size_t)k * bytes + s.offset;
-            const void* from = p;
-            if (s.base == (uint64_t)(uintptr_t)c->sync) {
-                uint32_t* w = words.data() + sw * (size_t)k;
-                memcpy(w, p, sizeof(uint32_t) * sw);
-                for (int g = 0; g < desc[k].groups; g++)
-                    w[ekf::SYNC_WG0 + g] = ekf::image_retag(w[ekf::SYNC_WG0 + g], desc[k].epoch, c->scan_epoch);
-                from = w;
-            }
-            HIP_TRY(hipMemcpyAsync((void*)(uintptr_t)(s.base + (uint64_t)inst[k] * s.bytes), from, s.bytes,
-                                   hipMemcpyHostToDevice, c->stream));
-        }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    image_adopt(c, inst, K, desc);
-    return end_read(c);   // (pipelined: the next flush on D behind the copies, as ekf_resample)
-}
-
-extern "C" int ekf_export_instances_device(ekf_ctx* c, const int32_t* inst, int K, void* d_images, ekf_image_desc* desc)
-{
-    int rc = image_args(c, inst, K, d_images, desc);
-    if (rc || K == 0) return rc;
-    if ((uintptr_t)d_images & 3) return EKF_EINVAL;
-    const std::vector<ekf::ResampleArray> arrays = image_arrays_of(c);
-    const std::vector<ekf::CopySeg> table = ekf::image_export_plan(arrays, inst, K, (uint64_t)(uintptr_t)d_images);
-    rc = rs_stage(c, table);
-    if (rc) return rc;
-    rc = rs_wait(c);
-    if (rc) return rc;
-    HIP_TRY(ekf::launch_image(c->rs_host_dev, (int)table.size(), c->scan_epoch, c->ncu, c->stream));
-    rc = rs_launched(c);
-    if (rc) return rc;
-    image_describe(c, inst, K, ekf::image_bytes(arrays), desc);
-    return end_read(c);   // (pipelined: the next flush writes X[base] only after this read)
-}
-
-extern "C" int ekf_import_instances_device(ekf_ctx* c, const int32_t* inst, int K, const void* d_images,
-                                           const ekf_image_desc* desc)
-{
-    int rc = image_args(c, inst, K, d_images, desc);
-    if (rc || K == 0) return rc;
-    if ((uintptr_t)d_images & 3) return EKF_EINVAL;
-    const std::vector<ekf::ResampleArray> arrays = image_arrays_of(c);
-    rc = image_congruent(c, inst, K, ekf::image_bytes(arrays), desc);
-    if (rc) return rc;
-    std::vector<uint32_t> epochs((size_t)K);
-    for (int k = 0; k < K; k++) epochs[(size_t)k] = desc[k].epoch;
-    const std::vector<ekf::CopySeg> table =
-        ekf::image_import_plan(arrays, (uint64_t)(uintptr_t)c->sync, ekf::SYNC_WG0, c->last_G, inst, epochs.data(), K,
-                               (uint64_t)(uintptr_t)d_images);
-    rc = rs_stage(c, table);
-    if (rc) return rc;
-    rc = rs_wait(c);
-    if (rc) return rc;
-    HIP_TRY(ekf::launch_image(c->rs_host_dev, (int)table.size(), c->scan_epoch, c->ncu, c->stream));
-    rc = rs_launched(c);
-    if (rc) return rc;
-    image_adopt(c, inst, K, desc);
-    return end_read(c);   // (pipelined: the next flush on D behind the copy, as ekf_resample)
 }
 
 extern "C" size_t ekf_landmark_block_bytes(const ekf_ctx* c)

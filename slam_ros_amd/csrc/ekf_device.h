@@ -529,6 +529,52 @@ __device__ __forceinline__ void pll_block(const PllView<T>& v, int i0, int j0, d
     out[0] = o[0][0]; out[1] = o[0][1]; out[2] = o[0][2]; out[3] = o[0][3];
 }
 
+// ---- the read-only view (ReadView) of unit_query.hip, unit_gate.hip and unit_joint.hip ----
+// sh_ctl[PMAX] (LDS) of instance e from the pending steps' result records; the caller's barrier follows
+__device__ __forceinline__ void view_ctl(const ReadView& v, const Slot* pend, int e, int4* sh_ctl)
+{
+    const int tid = threadIdx.x;
+    if (tid < v.npend) {
+        // (a rolled-back step reads as a no-op: no reset, ks = 0, no rows)
+        const int* r = pend[tid].res + (size_t)e * RES_STRIDE;
+        sh_ctl[tid] = make_int4(r[RES_RESET], r[RES_KSTEPS], r[RES_NADD], r[RES_SAVED_IN]);
+    }
+}
+
+// instance e's landmark block with the pending steps applied on read
+template <typename T>
+__device__ __forceinline__ PllView<T> view_pll(const ReadView& v, const Slot* pend, int e, const int4* sh_ctl)
+{
+    const Dims& d = v.d;
+    PllView<T> pv;
+    pv.X = reinterpret_cast<const T*>(v.Pread) + (size_t)e * d.ntiles * TILE_ELEMS;
+    pv.nb = d.nb;
+    pv.kmax = d.kmax;
+    pv.M = d.M;
+    pv.max_lines = d.max_lines;
+    pv.e = e;
+    pv.ex = storage_exp<T>(v.pexp, e);
+    pv.opstride = (size_t)d.nb * 64 * (d.kmax / 2);
+    pv.usym = v.usym;
+    pv.us = v.usym ? -ldexpf(1.0f, pv.ex) : 1.0f;
+    pv.npend = v.npend;
+    pv.pend = pend;
+    pv.ctl = sh_ctl;
+    pv.rnd = !v.bf;
+    return pv;
+}
+
+// the committed copy of instance e's robot strip ([3][n]) and mean ([n])
+struct Committed {
+    const double* Rs;
+    const double* y;
+};
+__device__ __forceinline__ Committed view_committed(const ReadView& v, int e)
+{
+    const int cb = v.live[e] & 1;
+    return {v.Rs + ((size_t)cb * v.Etot + e) * 3 * v.d.n, v.y + ((size_t)cb * v.Etot + e) * v.d.n};
+}
+
 // the to-storage rounding a split-plane group's flush applies once (fp16 storage, `once` = a
 // split-plane context; the per-step rounding of the exact arithmetic already happened in pll_block:
 // PllView::rnd): the reads that leave the state untouched (unit_query.hip, unit_gate.hip) apply it

@@ -1,7 +1,8 @@
 // ekf_gate.h — the gate arithmetic of the association (Robot.cpp:313-498): the 5×5 block of a
 // candidate, its innovation covariance and innovation, the exact fp64 evaluation with the gate
 // decision and the storage precision of the gate. Shared by the association kernels (ekf_kernels.hip)
-// and the gate query (unit_gate.hip), so that both evaluate a candidate bit for bit alike.
+// and the gate queries (unit_gate.hip, unit_joint.hip: trial_robot, trial_block), so that all evaluate a
+// candidate bit for bit alike.
 #pragma once
 
 #include "ekf_device.h"
@@ -48,22 +49,6 @@ struct Block5 {
     double p0a, p1a, p2a, p0b, p1b, p2b;
     double daa, dab, dba, dbb;
 };
-
-__device__ __forceinline__ void load_block5(Block5& b, int j, const double* R33, const double* Rs,
-                                            int n, const double Dj[4])
-{
-    const int l0 = 3 + 2 * j;
-    b.p00 = R33[0]; b.p01 = R33[1]; b.p02 = R33[2];
-    b.p10 = R33[3]; b.p11 = R33[4]; b.p12 = R33[5];
-    b.p20 = R33[6]; b.p21 = R33[7]; b.p22 = R33[8];
-    const double2 ra = *reinterpret_cast<const double2*>(Rs + l0);
-    const double2 rb = *reinterpret_cast<const double2*>(Rs + n + l0);
-    const double2 rc = *reinterpret_cast<const double2*>(Rs + 2 * n + l0);
-    b.p0a = ra.x; b.p0b = ra.y;
-    b.p1a = rb.x; b.p1b = rb.y;
-    b.p2a = rc.x; b.p2b = rc.y;
-    b.daa = Dj[0]; b.dab = Dj[1]; b.dba = Dj[2]; b.dbb = Dj[3];
-}
 
 // S = H·P5·Hᵀ + R in the reference's summation order (Robot.cpp:397-405); also returns the
 // intermediate rows hp0 = hr0·P5, hp1 = hr1·P5 (hr0 = (0,0,-1,1,0), hr1 = (h10,h11,0,h1l,1)).
@@ -185,8 +170,7 @@ __device__ __forceinline__ void fill_block5(Block5& b5, const double R33[9], dou
 // x_pre, F3 and the predicted 3×3 block of instance e from the committed pose and strip
 // (Robot.cpp:130-258), expression for expression the PHASE_PREDICT branch of scan_kernel, so that a
 // gate (unit_gate.hip, unit_joint.hip) with an encoder pose sees what ekf_predict would commit, bit for bit
-template <typename P>   // GateParams or JointParams: pose, enc_noise
-__device__ __forceinline__ void gate_predict(const P& p, int e, const double* enc, double R33[9],
+__device__ __forceinline__ void gate_predict(const TrialLines& p, int e, const double* enc, double R33[9],
                                              double xp[3], double F3[9])
 {
     const double x0 = p.pose[3 * e + 0], y0 = p.pose[3 * e + 1], t0 = p.pose[3 * e + 2];
@@ -225,6 +209,61 @@ __device__ __forceinline__ void gate_predict(const P& p, int e, const double* en
             }
             R33[a * 3 + b] = s + t;
         }
+}
+
+// ---- a trial line's candidate (unit_gate.hip, unit_joint.hip): one sequence from the state to the
+// Block5 handed to eval_candidate, so that both kernels evaluate a candidate on the same bits ----
+
+// the lines of launch row `row`
+__device__ __forceinline__ int trial_count(const TrialLines& t, int row, int max_lines)
+{
+    return t.nlines ? min(max(t.nlines[row], 0), max_lines) : t.L;
+}
+
+// The robot side of a trial of instance e (launch row `row`): the 3×3 block of the committed strip
+// Rs ([3][n]) and the pose the lines are seen from. With an encoder pose the predict is applied on read
+// (F3: rows 0..2 of its Fx, else the identity); without one it is x_pre between ekf_predict and
+// ekf_update, else the committed pose.
+struct TrialRobot {
+    double R33[9], xp[3], F3[9];
+};
+__device__ __forceinline__ void trial_robot(const TrialLines& t, int e, int row, const double* Rs, int n,
+                                            TrialRobot& rb)
+{
+#pragma unroll
+    for (int a = 0; a < 9; a++) {
+        rb.R33[a] = Rs[(a / 3) * n + (a % 3)];
+        rb.F3[a] = a % 4 == 0 ? 1.0 : 0.0;
+    }
+    if (t.enc) {
+        gate_predict(t, e, t.enc + 3 * row, rb.R33, rb.xp, rb.F3);
+    } else {
+        const double* x = (t.use_xpre ? t.xpre : t.pose) + 3 * e;
+        rb.xp[0] = x[0]; rb.xp[1] = x[1]; rb.xp[2] = x[2];
+    }
+}
+
+// Landmark j's side: its diagonal block as the queries read it (pll_block with the pending steps, then
+// query_round), its columns of the strip (predicted when there is motion) and its mean yb, and the
+// 5×5 block of the two. The columns are returned too: the joint gate's pairs need them.
+struct TrialBlock {
+    Block5 b5;
+    double2 rr0, rr1, rr2, yb;
+};
+template <typename T>
+__device__ __forceinline__ void trial_block(const PllView<T>& pv, bool once, bool motion, const TrialRobot& rb,
+                                            const Committed& cm, int n, int j, TrialBlock& tb)
+{
+    double Dj[4];
+    pll_block<T>(pv, 2 * j, 2 * j, Dj);
+    query_round<T>(once, pv.ex, Dj);
+    const int b0 = 3 + 2 * j;
+    tb.rr0 = *reinterpret_cast<const double2*>(cm.Rs + b0);
+    tb.rr1 = *reinterpret_cast<const double2*>(cm.Rs + n + b0);
+    tb.rr2 = *reinterpret_cast<const double2*>(cm.Rs + 2 * n + b0);
+    tb.yb = *reinterpret_cast<const double2*>(cm.y + b0);
+    if (motion) predict_cols(rb.F3, tb.rr0, tb.rr1, tb.rr2);
+    fill_block5(tb.b5, rb.R33, tb.rr0, tb.rr1, tb.rr2, Dj);
 }
 
 }  // namespace ekf

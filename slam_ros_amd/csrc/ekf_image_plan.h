@@ -1,6 +1,6 @@
 // ekf_image_plan.h — the instance image of ekf_export_instances / ekf_import_instances (slam_ekf.h):
 // everything an instance owns in a position-independent form, and the copy tables that write it
-// from a context and read it into a slot of another. Host only (no HIP include): ekf_api.hip fills a
+// from a context and read it into a slot of another. Host only (no HIP include): ekf_copy.hip fills a
 // ResampleLayout from the context and hands the tables to launch_image (unit_image.hip);
 // tests/cpp/image_driver.cpp checks them on a CPU.
 //

@@ -1,4 +1,4 @@
-// ekf_kernels.h — launch parameters and launchers shared by the kernels' units (unit_*.hip) and ekf_api.hip.
+// ekf_kernels.h — launch parameters and launchers shared by the kernels' units (unit_*.hip) and the host units (ekf_*.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -248,22 +248,14 @@ struct DowndateParams {
     Slot steps[PMAX];
 };
 
-// Covariance blocks of chosen landmarks, read as the next association kernel would read them: the
-// landmark block Pread with the pending steps applied on read (pll_block), the robot strip and the
-// mean from the committed copy live[e]. Nothing of the state is written (unit_query.hip).
-//   QUERY_JOINT      cov [E][(3+2K)²] rows / columns {0, 1, 2, 3+2j, 4+2j : j in landmarks}, mean [E][3+2K]
-//   QUERY_MARGINALS  blocks [E][K][4], cross [E][K][6] = P[0:3, 3+2j : 5+2j], mean [E][K][2]
-// An index outside [0, N) is never dereferenced: its entries are NaN.
-enum { QUERY_JOINT = 0, QUERY_MARGINALS = 1 };
-constexpr int QUERY_THREADS = 256;   // joint: four waves, one row landmark each, 64 column landmarks wide
-constexpr int QUERY_ROWS = QUERY_THREADS / 64;
-struct QueryParams {
+// The read-only view every kernel that leaves the state untouched takes (unit_query.hip, unit_gate.hip,
+// unit_joint.hip), which is the view of the next association kernel: the landmark block Pread with the
+// pending steps applied on read (pll_block), the robot strip and the mean from the committed copy
+// live[e]. The host fills it in begin_read, the kernels read it through ekf_device.h's view_* helpers. The
+// pending steps' slots go with it as the last member pend[PMAX] of each parameter block (oldest first).
+struct ReadView {
     Dims d;
-    int mode;
-    int E;                // instances in this launch (grid.y): outputs and index lists are per launch row
-    int e0;               // first instance of this launch
     int Etot;             // instances of the context
-    int K;                // landmarks queried per instance
     int usym;             // symmetric fp32 operands (ScanParams::usym)
     int bf;               // split-plane context: fp16 storage rounded once, after the pending steps
     int npend;            // steps not yet in Pread, applied on read (in order)
@@ -272,19 +264,49 @@ struct QueryParams {
     const double* y;      // [2][Etot][n]
     const int* live;      // [Etot]
     const int* pexp;      // [Etot]
+};
+
+// What the gate and the joint gate read besides the view: the committed pose, the gate's constants and
+// the trial lines, each line gated as the first line of a scan. Lines and encoder poses are per launch
+// row (instance e0 + row), max_lines apart.
+struct TrialLines {
+    const double* pose;   // [Etot][3] committed pose
+    const double* xpre;   // [Etot][3] x_pre of the last ekf_predict
+    const int* saved;     // [Etot]
+    int use_xpre;         // enc == nullptr: 1 between ekf_predict and ekf_update (x_pre), 0 the pose
+    int r_mode;
+    int L;                // lines of every row (nlines == nullptr: the host form)
+    double gate, enc_noise;
+    const double* enc;    // [E][3] (per launch row) the predict is applied on read; nullptr: no motion
+    const ekf_line* lines;// [E][max_lines]
+    const int* nlines;    // [E] (the device form), or nullptr (the host form)
+};
+
+// Covariance blocks of chosen landmarks (unit_query.hip). Nothing of the state is written.
+//   QUERY_JOINT      cov [E][(3+2K)²] rows / columns {0, 1, 2, 3+2j, 4+2j : j in landmarks}, mean [E][3+2K]
+//   QUERY_MARGINALS  blocks [E][K][4], cross [E][K][6] = P[0:3, 3+2j : 5+2j], mean [E][K][2]
+// An index outside [0, N) is never dereferenced: its entries are NaN.
+enum { QUERY_JOINT = 0, QUERY_MARGINALS = 1 };
+constexpr int QUERY_THREADS = 256;   // joint: four waves, one row landmark each, 64 column landmarks wide
+constexpr int QUERY_ROWS = QUERY_THREADS / 64;
+struct QueryParams {
+    ReadView v;
+    int mode;
+    int E;                // instances in this launch (grid.y): outputs and index lists are per launch row
+    int e0;               // first instance of this launch
+    int K;                // landmarks queried per instance
     const int32_t* landmarks;   // [E][K] (device-readable; nullptr: 0 .. K − 1)
     double* cov;          // QUERY_JOINT (nullptr: the mean only)
     double* mean;
     double* blocks;       // QUERY_MARGINALS
     double* cross;
-    Slot pend[PMAX];      // pending steps, oldest first
+    Slot pend[PMAX];      // (ReadView)
 };
 hipError_t launch_query(const QueryParams& p, int precision, hipStream_t st);
 
-// Trial lines gated against every saved landmark (unit_gate.hip), each as the first line of a scan;
-// the same read-only view as QueryParams (its first fields, filled by the same preamble), plus the
-// committed pose. Lines, hit records and distances are per launch row (instance e0 + row), max_lines
-// apart; flags and part are the context's scratch.
+// Trial lines gated against every saved landmark (unit_gate.hip). Hit records and distances are per
+// launch row, max_lines apart (the device form writes unused hit entries as empty); flags and part are
+// the context's scratch.
 constexpr int GATE_THREADS = 256;   // pass 1: landmarks per workgroup, one partial record per wave
 enum { GATE_FL_SINGULAR = 1, GATE_FL_AMB = 2 };   // per-candidate flag byte
 struct GatePart {      // one wave's 64 landmarks against one line
@@ -296,71 +318,34 @@ struct GatePart {      // one wave's 64 landmarks against one line
     double cn[7];      // ... of nearest
 };
 struct GateParams {
-    Dims d;
+    ReadView v;
+    TrialLines t;
     int E;                // instances in this launch (grid.y)
     int e0;               // first instance of this launch
-    int Etot;             // instances of the context
-    int usym;             // symmetric fp32 operands (ScanParams::usym)
-    int bf;               // split-plane context: fp16 storage rounded once, after the pending steps
-    int npend;            // steps not yet in Pread, applied on read (in order)
-    const void* Pread;    // [Etot][ntiles][1024]
-    const double* Rs;     // [2][Etot][3][n]
-    const double* y;      // [2][Etot][n]
-    const int* live;      // [Etot]
-    const int* pexp;      // [Etot]
-    const double* pose;   // [Etot][3] committed pose
-    const double* xpre;   // [Etot][3] x_pre of the last ekf_predict
-    const int* saved;     // [Etot]
-    int use_xpre;         // enc == nullptr: 1 between ekf_predict and ekf_update (x_pre), 0 the pose
-    int r_mode;
-    int L;                // lines of every row (nlines == nullptr: the host form)
-    int nw;               // partial records per line: ⌈N / 64⌉
-    double gate, enc_noise;
-    const double* enc;    // [E][3] (per launch row) the predict is applied on read; nullptr: no motion
-    const ekf_line* lines;// [E][max_lines]
-    const int* nlines;    // [E] (the device form: unused hit entries are written as empty); or nullptr
     ekf_gate_hit* hits;   // [E][max_lines]
     double* d2;           // [E][max_lines][N] or nullptr
     unsigned char* flags; // [E][max_lines][N]
-    GatePart* part;       // [E][max_lines][nw]
-    Slot pend[PMAX];      // pending steps, oldest first
+    GatePart* part;       // [E][max_lines][gate_waves(N)]
+    Slot pend[PMAX];      // (ReadView)
 };
+constexpr int gate_waves(int N) { return (N + 63) / 64; }   // partial records per line
 hipError_t launch_gate(const GateParams& p, int precision, hipStream_t st);
 
-// Joint compatibility of hypotheses (unit_joint.hip): per launch row (instance e0 + row) H assignments
-// of the row's lines to landmarks; the view of GateParams (the same preamble), one workgroup per
-// (hypothesis, row). assign and d2_each are `astride` apart per hypothesis (L in the host form,
-// max_lines in the device form); the kernel needs no scratch but its LDS.
+// Joint compatibility of hypotheses (unit_joint.hip): per launch row H assignments of the row's lines
+// to landmarks, one workgroup per (hypothesis, row). assign and d2_each are `astride` apart per
+// hypothesis (L in the host form, max_lines in the device form); the kernel needs no scratch but its LDS.
 constexpr int JOINT_THREADS = 256;
 struct JointParams {
-    Dims d;
+    ReadView v;
+    TrialLines t;
     int E;                // instances in this launch (grid.y)
     int e0;               // first instance of this launch
-    int Etot;             // instances of the context
-    int usym;             // symmetric fp32 operands (ScanParams::usym)
-    int bf;               // split-plane context: fp16 storage rounded once, after the pending steps
-    int npend;            // steps not yet in Pread, applied on read (in order)
-    const void* Pread;    // [Etot][ntiles][1024]
-    const double* Rs;     // [2][Etot][3][n]
-    const double* y;      // [2][Etot][n]
-    const int* live;      // [Etot]
-    const int* pexp;      // [Etot]
-    const double* pose;   // [Etot][3] committed pose
-    const double* xpre;   // [Etot][3] x_pre of the last ekf_predict
-    const int* saved;     // [Etot]
-    int use_xpre;         // enc == nullptr: 1 between ekf_predict and ekf_update (x_pre), 0 the pose
-    int r_mode;
-    int L;                // lines of every row (nlines == nullptr: the host form)
     int H;                // hypotheses per row (grid.x)
     int astride;          // entries per hypothesis in assign and d2_each
-    double gate, enc_noise;
-    const double* enc;    // [E][3] (per launch row) the predict is applied on read; nullptr: no motion
-    const ekf_line* lines;// [E][max_lines]
-    const int* nlines;    // [E], or nullptr (the host form)
     const int32_t* assign;// [E][H][astride]
     ekf_joint_hit* hits;  // [E][H]
     double* d2_each;      // [E][H][astride] or nullptr
-    Slot pend[PMAX];      // pending steps, oldest first
+    Slot pend[PMAX];      // (ReadView)
 };
 hipError_t launch_joint(const JointParams& p, int precision, hipStream_t st);
 size_t joint_lds_bytes(int max_lines);   // dynamic LDS of the joint kernel (the packed factor)

@@ -1,5 +1,5 @@
 // ekf_resample_plan.h — the copy table of ekf_resample (slam_ekf.h): which bytes instance e takes
-// from instance src[e]. Host only (no HIP include): ekf_api.hip fills a ResampleLayout from the
+// from instance src[e]. Host only (no HIP include): ekf_copy.hip fills a ResampleLayout from the
 // context and hands the table to launch_resample (unit_resample.hip); tests/cpp/resample_driver.cpp
 // checks it on a CPU.
 //

@@ -36,16 +36,12 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_pass1_kernel(GateParams p)
     const int tid = threadIdx.x;
     const int row = blockIdx.y;        // the launch's row: lines and outputs
     const int e = p.e0 + row;          // the instance
-    const Dims d = p.d;
-    const int L = p.nlines ? min(max(p.nlines[row], 0), d.max_lines) : p.L;
+    const Dims d = p.v.d;
+    const int L = trial_count(p.t, row, d.max_lines);
     if (L <= 0) return;   // (uniform)
-    if (tid < p.npend) {
-        // (a rolled-back step reads as a no-op: no reset, ks = 0, no rows)
-        const int* r = p.pend[tid].res + (size_t)e * RES_STRIDE;
-        sh_ctl[tid] = make_int4(r[RES_RESET], r[RES_KSTEPS], r[RES_NADD], r[RES_SAVED_IN]);
-    }
+    view_ctl(p.v, p.pend, e, sh_ctl);
     {
-        const double* src = reinterpret_cast<const double*>(p.lines + (size_t)row * d.max_lines);
+        const double* src = reinterpret_cast<const double*>(p.t.lines + (size_t)row * d.max_lines);
         double* dst = reinterpret_cast<double*>(sh_lines);
         for (int k = tid; k < L * 6; k += GATE_THREADS) dst[k] = src[k];
     }
@@ -54,54 +50,18 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_pass1_kernel(GateParams p)
     const int j = (int)blockIdx.x * GATE_THREADS + tid;   // the owned landmark
     const int wv = j >> 6;                                // its wave's partial record
     if ((j & ~63) >= d.N) return;                         // (a wave past the map: wave-uniform)
-    const int n = d.n;
-    const int saved = min(max(p.saved[e], 0), d.N);
+    const int saved = min(max(p.t.saved[e], 0), d.N);
     const bool cand = j < saved;
-    const int cb = p.live[e] & 1;   // the committed copy of the strip and the mean
-    const double* Rs = p.Rs + ((size_t)cb * p.Etot + e) * 3 * n;
-    const double* y = p.y + ((size_t)cb * p.Etot + e) * n;
+    const Committed cm = view_committed(p.v, e);
+    TrialRobot rb;
+    trial_robot(p.t, e, row, cm.Rs, d.n, rb);
 
-    double R33[9], xp[3];
-    double F3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-#pragma unroll
-    for (int a = 0; a < 9; a++) R33[a] = Rs[(a / 3) * n + (a % 3)];
-    if (p.enc) {
-        gate_predict(p, e, p.enc + 3 * row, R33, xp, F3);
-    } else {
-        const double* x = (p.use_xpre ? p.xpre : p.pose) + 3 * e;
-        xp[0] = x[0]; xp[1] = x[1]; xp[2] = x[2];
-    }
-
-    Block5 b5;
+    TrialBlock tb;
     double ma = 0.0, mr = 0.0, sn = 0.0, cs = 1.0;
     if (cand) {
-        PllView<T> pv;
-        pv.X = reinterpret_cast<const T*>(p.Pread) + (size_t)e * d.ntiles * TILE_ELEMS;
-        pv.nb = d.nb;
-        pv.kmax = d.kmax;
-        pv.M = d.M;
-        pv.max_lines = d.max_lines;
-        pv.e = e;
-        pv.ex = storage_exp<T>(p.pexp, e);
-        pv.opstride = (size_t)d.nb * 64 * (d.kmax / 2);
-        pv.usym = p.usym;
-        pv.us = p.usym ? -ldexpf(1.0f, pv.ex) : 1.0f;
-        pv.npend = p.npend;
-        pv.pend = p.pend;
-        pv.ctl = sh_ctl;
-        pv.rnd = !p.bf;
-        double Dj[4];
-        pll_block<T>(pv, 2 * j, 2 * j, Dj);
-        query_round<T>(p.bf != 0, pv.ex, Dj);
-        const int b0 = 3 + 2 * j;
-        double2 rr0 = *reinterpret_cast<const double2*>(Rs + b0);
-        double2 rr1 = *reinterpret_cast<const double2*>(Rs + n + b0);
-        double2 rr2 = *reinterpret_cast<const double2*>(Rs + 2 * n + b0);
-        const double2 yb = *reinterpret_cast<const double2*>(y + b0);
-        if (p.enc) predict_cols(F3, rr0, rr1, rr2);
-        fill_block5(b5, R33, rr0, rr1, rr2, Dj);
-        ma = yb.x;
-        mr = yb.y;
+        trial_block<T>(view_pll<T>(p.v, p.pend, e, sh_ctl), p.v.bf != 0, p.t.enc != nullptr, rb, cm, d.n, j, tb);
+        ma = tb.yb.x;
+        mr = tb.yb.y;
         sincos(ma, &sn, &cs);
     }
 
@@ -115,8 +75,8 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_pass1_kernel(GateParams p)
         double an = inf;   // |d2|; +inf: no candidate or a NaN distance (never the nearest)
         if (cand) {
             double Rm[4];
-            line_R(sh_lines[i], i, p.r_mode, Rm);
-            eval_candidate<true>(b5, ma, mr, sn, cs, xp, sh_lines[i].alpha, sh_lines[i].r, Rm, p.gate, eta, c);
+            line_R(sh_lines[i], i, p.t.r_mode, Rm);
+            eval_candidate<true>(tb.b5, ma, mr, sn, cs, rb.xp, sh_lines[i].alpha, sh_lines[i].r, Rm, p.t.gate, eta, c);
             pass = c.pass;
             fl = (c.singular ? GATE_FL_SINGULAR : 0) | (c.amb ? GATE_FL_AMB : 0);
             const double a = fabs(c.d2);
@@ -134,7 +94,7 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_pass1_kernel(GateParams p)
         for (int off = 32; off > 0; off >>= 1) best = fmin(best, __shfl_xor(best, off, 64));
         const unsigned long long mn = __ballot(cand && an == best && best < inf);
         const int lf = first_lane(mp), ln = first_lane(mn);
-        GatePart* part = p.part + li * p.nw + wv;
+        GatePart* part = p.part + li * gate_waves(d.N) + wv;
         if (lane == 0) {
             part->first = lf < 64 ? (j + lf) : -1;
             part->nearest = ln < 64 ? (j + ln) : -1;
@@ -153,8 +113,8 @@ __global__ __launch_bounds__(64) void gate_pass2_kernel(GateParams p)
     const int i = blockIdx.x;
     const int row = blockIdx.y;
     const int e = p.e0 + row;
-    const Dims d = p.d;
-    const int L = p.nlines ? min(max(p.nlines[row], 0), d.max_lines) : p.L;
+    const Dims d = p.v.d;
+    const int L = trial_count(p.t, row, d.max_lines);
     const size_t li = (size_t)row * d.max_lines + i;
     ekf_gate_hit* hit = p.hits + li;
     const double nan = __builtin_nan("");
@@ -170,8 +130,8 @@ __global__ __launch_bounds__(64) void gate_pass2_kernel(GateParams p)
         if (lane == 0) *hit = h;
         return;
     }
-    const int saved = min(max(p.saved[e], 0), d.N);
-    const GatePart* part = p.part + li * p.nw;
+    const int saved = min(max(p.t.saved[e], 0), d.N);
+    const GatePart* part = p.part + li * gate_waves(d.N);
     const int nwu = (saved + 63) >> 6;   // the waves that held a candidate
     int wf = 0x7fffffff, wn = 0x7fffffff, np = 0;
     double best = inf;
@@ -229,12 +189,13 @@ __global__ __launch_bounds__(64) void gate_pass2_kernel(GateParams p)
 
 hipError_t launch_gate(const GateParams& p, int precision, hipStream_t st)
 {
-    if (p.E < 1 || p.npend < 0 || p.npend > PMAX || p.L < 0 || p.L > p.d.max_lines || p.d.max_lines > EKF_MAX_LINES ||
-        p.nw != (p.d.N + 63) / 64 || !p.hits || !p.flags || !p.part)
+    const Dims& d = p.v.d;
+    if (p.E < 1 || p.v.npend < 0 || p.v.npend > PMAX || p.t.L < 0 || p.t.L > d.max_lines || d.max_lines > EKF_MAX_LINES ||
+        !p.hits || !p.flags || !p.part)
         return hipErrorInvalidValue;
-    const int rows = p.nlines ? p.d.max_lines : p.L;   // hit records per instance
+    const int rows = p.t.nlines ? d.max_lines : p.t.L;   // hit records per instance
     if (rows == 0) return hipSuccess;
-    const dim3 g1((unsigned)((p.d.N + GATE_THREADS - 1) / GATE_THREADS), (unsigned)p.E);
+    const dim3 g1((unsigned)((d.N + GATE_THREADS - 1) / GATE_THREADS), (unsigned)p.E);
     if (precision == EKF_PREC_F64) hipLaunchKernelGGL(gate_pass1_kernel<double>, g1, dim3(GATE_THREADS), 0, st, p);
     else if (precision == EKF_PREC_F32) hipLaunchKernelGGL(gate_pass1_kernel<float>, g1, dim3(GATE_THREADS), 0, st, p);
     else if (precision == EKF_PREC_F16) hipLaunchKernelGGL(gate_pass1_kernel<_Float16>, g1, dim3(GATE_THREADS), 0, st, p);

@@ -40,19 +40,15 @@ __global__ __launch_bounds__(JOINT_THREADS) void joint_kernel(JointParams p)
     const int hyp = blockIdx.x;
     const int row = blockIdx.y;        // the launch's row: lines, hypotheses and outputs
     const int e = p.e0 + row;          // the instance
-    const Dims d = p.d;
-    const int L = p.nlines ? min(max(p.nlines[row], 0), d.max_lines) : p.L;
+    const Dims d = p.v.d;
+    const int L = trial_count(p.t, row, d.max_lines);
     const size_t ho = (size_t)row * p.H + hyp;
     const int32_t* asg = p.assign + ho * p.astride;
     double* each = p.d2_each ? p.d2_each + ho * p.astride : nullptr;
     ekf_joint_hit* hit = p.hits + ho;
     const double nan = __builtin_nan("");
 
-    if (tid < p.npend) {
-        // (a rolled-back step reads as a no-op: no reset, ks = 0, no rows)
-        const int* r = p.pend[tid].res + (size_t)e * RES_STRIDE;
-        sh_ctl[tid] = make_int4(r[RES_RESET], r[RES_KSTEPS], r[RES_NADD], r[RES_SAVED_IN]);
-    }
+    view_ctl(p.v, p.pend, e, sh_ctl);
     if (tid < 64) {
         // the assigned lines in list order; an entry outside [−1, N) is never used as an index
         const int a = tid < L ? asg[tid] : -1;
@@ -82,61 +78,27 @@ __global__ __launch_bounds__(JOINT_THREADS) void joint_kernel(JointParams p)
         return;
     }
     const int n2 = 2 * m;
-    const int n = d.n;
-    const int cb = p.live[e] & 1;   // the committed copy of the strip and the mean
-    const double* Rs = p.Rs + ((size_t)cb * p.Etot + e) * 3 * n;
-    const double* y = p.y + ((size_t)cb * p.Etot + e) * n;
-
-    PllView<T> pv;
-    pv.X = reinterpret_cast<const T*>(p.Pread) + (size_t)e * d.ntiles * TILE_ELEMS;
-    pv.nb = d.nb;
-    pv.kmax = d.kmax;
-    pv.M = d.M;
-    pv.max_lines = d.max_lines;
-    pv.e = e;
-    pv.ex = storage_exp<T>(p.pexp, e);
-    pv.opstride = (size_t)d.nb * 64 * (d.kmax / 2);
-    pv.usym = p.usym;
-    pv.us = p.usym ? -ldexpf(1.0f, pv.ex) : 1.0f;
-    pv.npend = p.npend;
-    pv.pend = p.pend;
-    pv.ctl = sh_ctl;
-    pv.rnd = !p.bf;
+    const Committed cm = view_committed(p.v, e);
+    const bool once = p.v.bf != 0;
+    const PllView<T> pv = view_pll<T>(p.v, p.pend, e, sh_ctl);
 
     // ---- per line: the gate's candidate, the diagonal block, v ----
     if (tid < m) {
         const int a = tid, j = sh_lm[a], i = sh_li[a];
-        double R33[9], xp[3];
-        double F3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-#pragma unroll
-        for (int q = 0; q < 9; q++) R33[q] = Rs[(q / 3) * n + (q % 3)];
-        if (p.enc) {
-            gate_predict(p, e, p.enc + 3 * row, R33, xp, F3);
-        } else {
-            const double* x = (p.use_xpre ? p.xpre : p.pose) + 3 * e;
-            xp[0] = x[0]; xp[1] = x[1]; xp[2] = x[2];
-        }
-        double Dj[4];
-        pll_block<T>(pv, 2 * j, 2 * j, Dj);
-        query_round<T>(p.bf != 0, pv.ex, Dj);
-        const int b0 = 3 + 2 * j;
-        double2 rr0 = *reinterpret_cast<const double2*>(Rs + b0);
-        double2 rr1 = *reinterpret_cast<const double2*>(Rs + n + b0);
-        double2 rr2 = *reinterpret_cast<const double2*>(Rs + 2 * n + b0);
-        const double2 yb = *reinterpret_cast<const double2*>(y + b0);
-        if (p.enc) predict_cols(F3, rr0, rr1, rr2);
-        Block5 b5;
-        fill_block5(b5, R33, rr0, rr1, rr2, Dj);
+        TrialRobot rb;
+        trial_robot(p.t, e, row, cm.Rs, d.n, rb);
+        TrialBlock tb;
+        trial_block<T>(pv, once, p.t.enc != nullptr, rb, cm, d.n, j, tb);
         double sn, cs;
-        sincos(yb.x, &sn, &cs);
-        const ekf_line ln = p.lines[(size_t)row * d.max_lines + i];
+        sincos(tb.yb.x, &sn, &cs);
+        const ekf_line ln = p.t.lines[(size_t)row * d.max_lines + i];
         double Rm[4];
-        line_R(ln, i, p.r_mode, Rm);
+        line_R(ln, i, p.t.r_mode, Rm);
         Cand c;
-        eval_candidate<true>(b5, yb.x, yb.y, sn, cs, xp, ln.alpha, ln.r, Rm, p.gate, gate_eta<T>(), c);
+        eval_candidate<true>(tb.b5, tb.yb.x, tb.yb.y, sn, cs, rb.xp, ln.alpha, ln.r, Rm, p.t.gate, gate_eta<T>(), c);
         if (each) each[i] = c.d2;
         double S[4], hp0[5], hp1[5];
-        innovation_cov(b5, c.h10, c.h11, c.h1l, Rm, S, hp0, hp1);   // (S == c.S; the hp rows are G)
+        innovation_cov(tb.b5, c.h10, c.h11, c.h1l, Rm, S, hp0, hp1);   // (S == c.S; the hp rows are G)
         double* w = sh_ln[a];
         w[JL_H10] = c.h10; w[JL_H11] = c.h11; w[JL_H1L] = c.h1l;
 #pragma unroll
@@ -144,9 +106,9 @@ __global__ __launch_bounds__(JOINT_THREADS) void joint_kernel(JointParams p)
             w[JL_G + k] = hp0[k];
             w[JL_G + 3 + k] = hp1[k];
         }
-        w[JL_C + 0] = rr0.x; w[JL_C + 1] = rr0.y;
-        w[JL_C + 2] = rr1.x; w[JL_C + 3] = rr1.y;
-        w[JL_C + 4] = rr2.x; w[JL_C + 5] = rr2.y;
+        w[JL_C + 0] = tb.rr0.x; w[JL_C + 1] = tb.rr0.y;
+        w[JL_C + 2] = tb.rr1.x; w[JL_C + 3] = tb.rr1.y;
+        w[JL_C + 4] = tb.rr2.x; w[JL_C + 5] = tb.rr2.y;
         // the lower half of the diagonal block (S[2], not S[1]) and the innovation
         A[tri(2 * a, 2 * a)] = c.S[0];
         A[tri(2 * a + 1, 2 * a)] = c.S[2];
@@ -165,7 +127,7 @@ __global__ __launch_bounds__(JOINT_THREADS) void joint_kernel(JointParams p)
         const int b = q - a * (a - 1) / 2;   // 0 <= b < a < m
         double Dab[4];
         pll_block<T>(pv, 2 * sh_lm[a], 2 * sh_lm[b], Dab);   // P[l_a, l_b] (transposed on read if stored so)
-        query_round<T>(p.bf != 0, pv.ex, Dab);
+        query_round<T>(once, pv.ex, Dab);
         const double* wa = sh_ln[a];
         const double* wb = sh_ln[b];
         const double h10 = wa[JL_H10], h11 = wa[JL_H11], h1l = wa[JL_H1L];
@@ -230,7 +192,7 @@ size_t joint_lds_bytes(int max_lines)
 template <typename T>
 static hipError_t launch_joint_t(const JointParams& p, hipStream_t st)
 {
-    const size_t lds = joint_lds_bytes(p.d.max_lines);
+    const size_t lds = joint_lds_bytes(p.v.d.max_lines);
     if (lds > 48 * 1024) {
         const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&joint_kernel<T>),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -242,8 +204,8 @@ static hipError_t launch_joint_t(const JointParams& p, hipStream_t st)
 
 hipError_t launch_joint(const JointParams& p, int precision, hipStream_t st)
 {
-    if (p.E < 1 || p.H < 0 || p.npend < 0 || p.npend > PMAX || p.L < 0 || p.L > p.d.max_lines ||
-        p.d.max_lines > EKF_MAX_LINES || p.astride < p.L || !p.hits || !p.assign || !p.lines)
+    if (p.E < 1 || p.H < 0 || p.v.npend < 0 || p.v.npend > PMAX || p.t.L < 0 || p.t.L > p.v.d.max_lines ||
+        p.v.d.max_lines > EKF_MAX_LINES || p.astride < p.t.L || !p.hits || !p.assign || !p.t.lines)
         return hipErrorInvalidValue;
     if (p.H == 0) return hipSuccess;
     if (precision == EKF_PREC_F64) return launch_joint_t<double>(p, st);

@@ -1,7 +1,7 @@
 // unit_query.hip — covariance blocks of chosen landmarks, read without a flush (ekf_query_joint,
 // ekf_query_marginals, ekf_query_joint_device).
 //
-// The kernel takes the view the next association kernel would take (QueryParams): the last
+// The kernel takes the view the next association kernel would take (ReadView): the last
 // materialised landmark block with the pending steps applied on read by pll_block — per step a reset,
 // the ordered FMA chain of the downdate, the augmented rows, the fp16 rounding — so under
 // EKF_ARITH_EXACT and on fp64 storage every value is bit for bit what the flush will store. On the
@@ -19,34 +19,17 @@ __global__ __launch_bounds__(QUERY_THREADS) void query_kernel(QueryParams p)
     const int tid = threadIdx.x;
     const int row = blockIdx.y;        // the launch's row: index list and outputs
     const int e = p.e0 + row;          // the instance
-    if (tid < p.npend) {
-        // (a rolled-back step reads as a no-op: no reset, ks = 0, no rows)
-        const int* r = p.pend[tid].res + (size_t)e * RES_STRIDE;
-        sh_ctl[tid] = make_int4(r[RES_RESET], r[RES_KSTEPS], r[RES_NADD], r[RES_SAVED_IN]);
-    }
+    view_ctl(p.v, p.pend, e, sh_ctl);
     __syncthreads();
-    const Dims d = p.d;
-    PllView<T> pv;
-    pv.X = reinterpret_cast<const T*>(p.Pread) + (size_t)e * d.ntiles * TILE_ELEMS;
-    pv.nb = d.nb;
-    pv.kmax = d.kmax;
-    pv.M = d.M;
-    pv.max_lines = d.max_lines;
-    pv.e = e;
-    pv.ex = storage_exp<T>(p.pexp, e);
-    pv.opstride = (size_t)d.nb * 64 * (d.kmax / 2);
-    pv.usym = p.usym;
-    pv.us = p.usym ? -ldexpf(1.0f, pv.ex) : 1.0f;
-    pv.npend = p.npend;
-    pv.pend = p.pend;
-    pv.ctl = sh_ctl;
-    pv.rnd = !p.bf;
+    const Dims d = p.v.d;
+    const bool once = p.v.bf != 0;
+    const PllView<T> pv = view_pll<T>(p.v, p.pend, e, sh_ctl);
 
     const int K = p.K;
     const int32_t* lm = p.landmarks ? p.landmarks + (size_t)row * K : nullptr;
-    const int cb = p.live[e] & 1;   // the committed copy of the strip and the mean
-    const double* Rs = p.Rs + ((size_t)cb * p.Etot + e) * 3 * d.n;
-    const double* y = p.y + ((size_t)cb * p.Etot + e) * d.n;
+    const Committed cm = view_committed(p.v, e);
+    const double* Rs = cm.Rs;
+    const double* y = cm.y;
     const double nan = __builtin_nan("");
 
     if (p.mode == QUERY_MARGINALS) {
@@ -57,7 +40,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void query_kernel(QueryParams p)
         double o[4] = {nan, nan, nan, nan};
         if (ok) {
             pll_block<T>(pv, 2 * j, 2 * j, o);
-            query_round<T>(p.bf != 0, pv.ex, o);
+            query_round<T>(once, pv.ex, o);
         }
         double* blk = p.blocks + ((size_t)row * K + k) * 4;
         double* cr = p.cross + ((size_t)row * K + k) * 6;
@@ -91,7 +74,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void query_kernel(QueryParams p)
         double o[4] = {nan, nan, nan, nan};
         if (ja >= 0 && ja < d.N && jb >= 0 && jb < d.N) {
             pll_block<T>(pv, 2 * ja, 2 * jb, o);
-            query_round<T>(p.bf != 0, pv.ex, o);
+            query_round<T>(once, pv.ex, o);
         }
         double* c0 = cov + (3 + 2 * (size_t)a) * nq + 3 + 2 * (size_t)b;
         c0[0] = o[0];
@@ -132,7 +115,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void query_kernel(QueryParams p)
 
 hipError_t launch_query(const QueryParams& p, int precision, hipStream_t st)
 {
-    if (p.K < 0 || p.K > p.d.N || p.E < 1 || p.npend < 0 || p.npend > PMAX) return hipErrorInvalidValue;
+    if (p.K < 0 || p.K > p.v.d.N || p.E < 1 || p.v.npend < 0 || p.v.npend > PMAX) return hipErrorInvalidValue;
     unsigned gx;
     if (p.mode == QUERY_MARGINALS) {
         if (p.K == 0) return hipSuccess;
