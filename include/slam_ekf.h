@@ -41,7 +41,8 @@ extern "C" {
  *    replicated). Added since, with the number unchanged (entry points only): ekf_query_joint,
  *    ekf_query_marginals, ekf_query_joint_device; ekf_gate_lines, ekf_gate_lines_device;
  *    ekf_gate_joint, ekf_gate_joint_device; ekf_resample, ekf_copy_instance;
- *    ekf_instance_image_bytes, ekf_export_instances(_device), ekf_import_instances(_device). */
+ *    ekf_instance_image_bytes, ekf_export_instances(_device), ekf_import_instances(_device);
+ *    ekf_associate_joint, ekf_associate_joint_device. */
 #define SLAM_EKF_ABI_VERSION 3
 #define EKF_MAX_LINES 64 /* lines per scan per instance; main.cpp:99 reserves 20 */
 
@@ -416,6 +417,75 @@ int ekf_gate_joint(ekf_ctx* ctx, int e, const double enc[3] /* may be NULL */, c
 int ekf_gate_joint_device(ekf_ctx* ctx, const double* d_enc /* [E][3] or NULL */, const ekf_line* d_lines /* [E][max_lines] */,
                           const int32_t* d_nlines /* [E] */, const int32_t* d_assign /* [E][H][max_lines] */, int H,
                           ekf_joint_hit* d_hits /* [E][H] */, double* d_d2_each /* [E][H][max_lines] or NULL */);
+
+/* The joint-compatibility search on the device, state untouched: given trial lines and each line's
+ * candidate landmarks, the jointly compatible assignment with the most pairings and, among those, the
+ * smallest joint distance (joint compatibility branch and bound). ekf_gate_joint scores hypotheses the
+ * caller forms; this call forms them itself, over a factor of S that grows two rows per pairing, so a
+ * scan costs one call instead of one ekf_gate_joint round trip per line. The reference has no such
+ * member (its association, Robot.cpp:313-498, is first-fit).
+ * Candidates: cand[i][c] is a landmark offered to line i, or -1. An entry is usable when it lies in
+ *   [0, savedLineCount); one at or past savedLineCount is skipped silently. An entry outside [-1, N)
+ *   is EKF_ERANGE in the host form; in the device form it is never used as an index, it is treated as
+ *   -1 and EKF_AS_INVALID is set. At most EKF_ASSOC_MAX_LINES lines may carry a usable candidate and at
+ *   most EKF_ASSOC_MAX_TOTAL candidates may be usable over all lines (the search's tables live in LDS:
+ *   64 candidates give 2016 pairs of one 2x2 block each, 16 pairings a packed factor of 33 rows): more
+ *   is EKF_ERANGE in the host form; in the device form that instance alone gets EKF_AS_INVALID and the
+ *   empty hypothesis.
+ * Duplicates: a landmark explains at most one line of a hypothesis (ekf_gate_joint allows a duplicate;
+ *   the search does not).
+ * Tree: the lines are taken in list order. At line i the children are its usable candidates in list
+ *   order (those not already taken on the path), then "unassigned" last. A child that assigns a pair is
+ *   kept only if its own joint distance satisfies d2 <= bound[m], m the pairings including the new one
+ *   (written so that NaN fails). A failed pivot of the factor prunes the child and sets
+ *   EKF_AS_SINGULAR. The empty hypothesis is always feasible.
+ * Result: among the leaves that are feasible at every assigning step, the largest m, then the smallest
+ *   d2 (fp64 compare), then the earliest in that depth-first order: a total order, so the answer does
+ *   not depend on how the device explores the tree. A subtree is cut only when it cannot beat the
+ *   incumbent strictly in (m, d2); d2 never decreases along a path (an fma sum of squares in ascending
+ *   k).
+ * Bits: d2 and logdet of the result are bit for bit what ekf_gate_joint returns for hit.assign at the
+ *   same point, in the host form and in the device form: v, H, R, the diagonal blocks and the pair
+ *   blocks S_ab are ekf_gate_joint's expressions (one copy); the factor row (r, .) is S_rc with its
+ *   updates fma(-L_rk, L_ck, .) in ascending k, then a division by L_cc, z carried as the extra row;
+ *   d2 = sum z_k^2 as an ascending fma chain and logdet = 2 sum log L_kk, the sum ascending.
+ * Budget: max_nodes in [1, EKF_ASSOC_MAX_NODES] (else EKF_ERANGE) bounds the children scored per
+ *   instance. When it runs out EKF_AS_TRUNCATED is set and the result is the best feasible hypothesis
+ *   found: still feasible, still with the bits above, but neither guaranteed optimal nor reproducible.
+ *   Without the flag the result is the unique optimum. The budget is dealt evenly to the search's
+ *   workgroups (8), and the first two levels of the tree are scored by each of them and count each
+ *   time, so a budget below a few hundred may end before the first leaf: the result is then the empty
+ *   hypothesis. Every loop of the kernels is bounded by the budget or by the caps; no kernel waits on
+ *   another workgroup.
+ * Pose and P: the three cases of ekf_gate_lines (enc given: predict on read; NULL between ekf_predict
+ *   and ekf_update: the predicted strip and x_pre; NULL otherwise: the committed pose), and its
+ *   EKF_EINVAL for enc != NULL between ekf_predict and ekf_update.
+ * No drain, no state change, as ekf_gate_lines. The host form is synchronous: one copy, one wait on
+ *   the context stream. The device form only enqueues; bound is shared by all instances.
+ * Errors: EKF_EINVAL for a NULL context, bound or hit, NULL lines or cand (the host form: with L > 0),
+ *   or a partitioned context;
+ *   EKF_ERANGE for e out of range, L outside [0, max_lines], C outside [1, EKF_ASSOC_MAX_CAND] or
+ *   max_nodes out of range. L == 0 is valid: the empty hypothesis, no launch. */
+#define EKF_ASSOC_MAX_CAND   8    /* C: candidates per line */
+#define EKF_ASSOC_MAX_LINES 16    /* lines that carry at least one usable candidate */
+#define EKF_ASSOC_MAX_TOTAL 64    /* usable candidates over all lines */
+#define EKF_ASSOC_MAX_NODES (1 << 22)
+enum { EKF_AS_TRUNCATED = 1, EKF_AS_SINGULAR = 2, EKF_AS_INVALID = 4 };   /* ekf_assoc_hit.status */
+typedef struct ekf_assoc_hit {
+    int32_t m;        /* pairings of the best hypothesis */
+    int32_t status;   /* EKF_AS_* */
+    int32_t nodes;    /* children scored; informational, not reproducible between runs */
+    int32_t reserved;
+    double d2, logdet;               /* of the best hypothesis; 0, 0 for m == 0 */
+    int32_t assign[EKF_MAX_LINES];   /* landmark per line or -1; entries >= L are -1 */
+} ekf_assoc_hit;
+int ekf_associate_joint(ekf_ctx* ctx, int e, const double enc[3] /* may be NULL */, const ekf_line* lines, int L,
+                        const int32_t* cand /* [L][C] */, int C, const double* bound /* [L+1] */,
+                        int max_nodes, ekf_assoc_hit* hit);
+int ekf_associate_joint_device(ekf_ctx* ctx, const double* d_enc /* [E][3] or NULL */, const ekf_line* d_lines /* [E][max_lines] */,
+                               const int32_t* d_nlines /* [E] */, const int32_t* d_cand /* [E][max_lines][C] */, int C,
+                               const double* d_bound /* [max_lines+1], shared by all instances */,
+                               int max_nodes, ekf_assoc_hit* d_hits /* [E] */);
 
 /* Instances copied onto others on the device: what acts on the weights the queries and gates give
  * (fork a hypothesis; drop the unlikely instances of an ensemble and duplicate the likely ones). The

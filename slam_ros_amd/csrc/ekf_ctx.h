@@ -1,6 +1,6 @@
 // ekf_ctx.h — the context behind the C-ABI and what its host units share (internal): ekf_api.hip (the
 // core: creation, the schedule, scans, flushes, state upload / download, the partitioned instance),
-// ekf_read.hip (the calls that read without draining: covariance queries, gate, joint gate) and
+// ekf_read.hip (the calls that read without draining: covariance queries, gate, joint gate, joint search) and
 // ekf_copy.hip (the calls that copy instances without draining: ekf_resample, the instance images).
 #pragma once
 
@@ -57,6 +57,12 @@ struct ekf_ctx {
     unsigned char* g_flags = nullptr;
     ekf::GatePart* g_part = nullptr;
     int predicted = 0;
+    // ekf_associate_joint: the rows' plans, candidate and pair tables and the search workgroups' records
+    // (ekf_kernels.h AssocParams; listed context memory, made on first use)
+    ekf::AssocPlan* as_plan = nullptr;
+    double* as_ctab = nullptr;
+    double* as_ptab = nullptr;
+    ekf::AssocRec* as_rec = nullptr;
     // ekf_resample and the device forms of the instance images: the copy table in pinned host memory
     // the kernel reads (sized to the largest call so far and kept), and the event behind the last
     // launch that reads it

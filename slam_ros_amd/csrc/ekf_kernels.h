@@ -249,7 +249,7 @@ struct DowndateParams {
 };
 
 // The read-only view every kernel that leaves the state untouched takes (unit_query.hip, unit_gate.hip,
-// unit_joint.hip), which is the view of the next association kernel: the landmark block Pread with the
+// unit_joint.hip, unit_assoc.hip), which is the view of the next association kernel: the landmark block Pread with the
 // pending steps applied on read (pll_block), the robot strip and the mean from the committed copy
 // live[e]. The host fills it in begin_read, the kernels read it through ekf_device.h's view_* helpers. The
 // pending steps' slots go with it as the last member pend[PMAX] of each parameter block (oldest first).
@@ -349,6 +349,60 @@ struct JointParams {
 };
 hipError_t launch_joint(const JointParams& p, int precision, hipStream_t st);
 size_t joint_lds_bytes(int max_lines);   // dynamic LDS of the joint kernel (the packed factor)
+
+// The joint-compatibility search (unit_assoc.hip; slam_ekf.h ekf_associate_joint): per launch row the
+// best jointly compatible assignment of the row's lines to their candidate landmarks, in three launches
+// with no wait between workgroups.
+//   tables  ASSOC_TG workgroups per row: the usable candidates in list order (AssocPlan), each one's v and
+//           diagonal block (ctab), and the 2×2 block S_ab of every pair of candidates on different lines
+//           with different landmarks (ptab, pair (a > b) at a(a − 1)/2 + b)
+//   search  ASSOC_W workgroups (one wave each) per row: depth first over the lines that carry a usable
+//           candidate, the nodes at depth ASSOC_SPLIT dealt round-robin; one record (AssocRec) each
+//   reduce  the best record of a row by (m, d2, depth-first order) into its ekf_assoc_hit
+// plan, ctab, ptab and rec are the context's scratch, per launch row.
+constexpr int ASSOC_THREADS = 256;  // tables: candidates, then pairs, one per thread
+constexpr int ASSOC_TG = 8;         // tables: workgroups per row (ASSOC_TG·ASSOC_THREADS >= ASSOC_PAIRS)
+constexpr int ASSOC_W = 8;          // search: workgroups per row
+constexpr int ASSOC_SPLIT = 2;      // search: the depth whose nodes are dealt to the workgroups
+constexpr int ASSOC_PAIRS = EKF_ASSOC_MAX_TOTAL * (EKF_ASSOC_MAX_TOTAL - 1) / 2;
+constexpr int ASSOC_CWORDS = 5;     // ctab words per candidate: v[2], S00, S10, S11
+struct AssocPlan {
+    int total;      // usable candidates (0 when a cap is exceeded)
+    int nactive;    // lines that carry one, in list order
+    int flags;      // EKF_AS_INVALID
+    int pad;
+    int lm[EKF_ASSOC_MAX_TOTAL];          // landmark of each usable candidate, in (line, list) order
+    int line[EKF_ASSOC_MAX_TOTAL];        // its line
+    int first[EKF_ASSOC_MAX_LINES + 1];   // first candidate of each active line; [nactive] = total
+    int aline[EKF_ASSOC_MAX_LINES];       // the active lines
+};
+struct AssocRec {
+    int valid;      // a leaf was reached
+    int m;
+    int flags;      // EKF_AS_TRUNCATED, EKF_AS_SINGULAR
+    int nodes;      // children scored
+    int order;      // number of the best leaf's ASSOC_SPLIT-deep ancestor in depth-first order
+    int pad[3];
+    double d2, logsum;
+    int pick[EKF_ASSOC_MAX_LINES];   // candidate per active line, −1: unassigned
+};
+struct AssocParams {
+    ReadView v;
+    TrialLines t;
+    int E;                // instances in this launch (grid.y)
+    int e0;               // first instance of this launch
+    int C;                // candidates per line
+    int budget;           // children each search workgroup may score (max_nodes / ASSOC_W)
+    const int32_t* cand;  // [E][max_lines][C] (one row in the host form: [L][C])
+    const double* bound;  // [L + 1] (the host form), [max_lines + 1] (the device form), shared by the rows
+    ekf_assoc_hit* hits;  // [E]
+    AssocPlan* plan;      // [E]
+    double* ctab;         // [E][EKF_ASSOC_MAX_TOTAL][ASSOC_CWORDS]
+    double* ptab;         // [E][ASSOC_PAIRS][4]
+    AssocRec* rec;        // [E][ASSOC_W]
+    Slot pend[PMAX];      // (ReadView)
+};
+hipError_t launch_assoc(const AssocParams& p, int precision, hipStream_t st);
 
 // ekf_resample's segmented copy (unit_resample.hip): the nseg entries of the host-built table
 // (ekf_resample_plan.h, device-readable), grid-strided over at most 32 workgroups per CU

@@ -1,6 +1,7 @@
 // ekf_read.hip — the calls that read the state without draining the flush (slam_ekf.h): the covariance
-// queries (ekf_query_*; kernel: unit_query.hip), the gate (ekf_gate_lines*; unit_gate.hip) and the joint
-// gate (ekf_gate_joint*; unit_joint.hip).
+// queries (ekf_query_*; kernel: unit_query.hip), the gate (ekf_gate_lines*; unit_gate.hip), the joint
+// gate (ekf_gate_joint*; unit_joint.hip) and the joint-compatibility search (ekf_associate_joint*;
+// unit_assoc.hip).
 //
 // Each kernel takes the view the next association kernel would take in enqueue() (ReadView): X[base]
 // once the event guarding it has passed, the steps [pend0, nsteps) applied on read, the committed copy
@@ -319,4 +320,99 @@ extern "C" int ekf_gate_joint_device(ekf_ctx* c, const double* d_enc, const ekf_
     jp.hits = d_hits;
     jp.d2_each = d_d2_each;
     return enqueue_joint(c, jp);
+}
+
+// ---- the joint-compatibility search (three launches on S; its tables are the context's scratch) ----
+static int enqueue_assoc(ekf_ctx* c, ekf::AssocParams& ap)
+{
+    if (!c->as_plan) {
+        const size_t E = (size_t)c->cfg.instances;
+        void* pl = nullptr;
+        void* ct = nullptr;
+        void* pt = nullptr;
+        void* rc = nullptr;
+        if (!dev_alloc(c, &pl, E * sizeof(ekf::AssocPlan)) ||
+            !dev_alloc(c, &ct, E * EKF_ASSOC_MAX_TOTAL * ekf::ASSOC_CWORDS * sizeof(double)) ||
+            !dev_alloc(c, &pt, E * ekf::ASSOC_PAIRS * 4 * sizeof(double)) ||
+            !dev_alloc(c, &rc, E * ekf::ASSOC_W * sizeof(ekf::AssocRec)))
+            return EKF_ENOMEM;   // (listed either way: free_all releases what was made)
+        c->as_ctab = (double*)ct;
+        c->as_ptab = (double*)pt;
+        c->as_rec = (ekf::AssocRec*)rc;
+        c->as_plan = (ekf::AssocPlan*)pl;
+    }
+    const int rc = begin_read(c, ap.v, ap.pend);
+    if (rc) return rc;
+    ap.plan = c->as_plan;
+    ap.ctab = c->as_ctab;
+    ap.ptab = c->as_ptab;
+    ap.rec = c->as_rec;
+    HIP_TRY(ekf::launch_assoc(ap, c->cfg.precision, c->stream));
+    return end_read(c);
+}
+
+// the checks both forms share, after trial_check
+static int assoc_check(int C, int max_nodes)
+{
+    if (C < 1 || C > EKF_ASSOC_MAX_CAND || max_nodes < 1 || max_nodes > EKF_ASSOC_MAX_NODES) return EKF_ERANGE;
+    return EKF_OK;
+}
+
+extern "C" int ekf_associate_joint(ekf_ctx* c, int e, const double enc[3], const ekf_line* lines, int L,
+                                   const int32_t* cand, int C, const double* bound, int max_nodes, ekf_assoc_hit* hit)
+{
+    if (!c || c->sh_world > 0 || (L > 0 && (!lines || !cand)) || !bound || !hit) return EKF_EINVAL;
+    int rc = trial_check(c, e, L, 0, enc);
+    if (!rc) rc = assoc_check(C, max_nodes);
+    if (rc) return rc;
+    const size_t LC = (size_t)L * C;
+    for (size_t k = 0; k < LC; k++)
+        if (cand[k] < -1 || cand[k] >= c->d.N) return EKF_ERANGE;
+    if (L == 0) {   // the empty hypothesis
+        memset(hit, 0, sizeof(*hit));
+        for (int i = 0; i < EKF_MAX_LINES; i++) hit->assign[i] = -1;
+        return EKF_OK;
+    }
+    // device scratch [hit], the pinned buffer [hit | lines | enc | bound | cand]
+    const size_t nh = sizeof(ekf_assoc_hit);
+    rc = host_form(c, nh, sizeof(ekf_line) * (size_t)L + sizeof(double) * (3 + (size_t)L + 1) + sizeof(int32_t) * LC);
+    if (rc) return rc;
+    size_t off = nh;
+    const ekf_line* p_lines = stage_input(c, &off, lines, (size_t)L);
+    const double* p_enc = stage_input(c, &off, enc, 3);
+    ekf::AssocParams ap{};
+    ap.E = 1;
+    ap.e0 = e;
+    ap.t = trial_lines(c, L, p_enc, p_lines, nullptr);
+    ap.C = C;
+    ap.budget = max_nodes / ekf::ASSOC_W;
+    ap.bound = stage_input(c, &off, bound, (size_t)L + 1);
+    ap.cand = stage_input(c, &off, cand, LC);
+    ap.hits = reinterpret_cast<ekf_assoc_hit*>(c->q_dev);
+    rc = enqueue_assoc(c, ap);
+    if (!rc) rc = fetch_results(c, nh);
+    if (rc) return rc;
+    memcpy(hit, c->q_pin.host, nh);
+    // (every entry was in [-1, N): what is left is a cap, EKF_ASSOC_MAX_LINES or EKF_ASSOC_MAX_TOTAL, which
+    // counts the usable candidates and so is known on the device only)
+    return (hit->status & EKF_AS_INVALID) ? EKF_ERANGE : EKF_OK;
+}
+
+extern "C" int ekf_associate_joint_device(ekf_ctx* c, const double* d_enc, const ekf_line* d_lines,
+                                          const int32_t* d_nlines, const int32_t* d_cand, int C, const double* d_bound,
+                                          int max_nodes, ekf_assoc_hit* d_hits)
+{
+    if (!c || c->sh_world > 0 || !d_lines || !d_nlines || !d_cand || !d_bound || !d_hits) return EKF_EINVAL;
+    int rc = trial_check(c, 0, 0, 0, d_enc);
+    if (!rc) rc = assoc_check(C, max_nodes);
+    if (rc) return rc;
+    ekf::AssocParams ap{};
+    ap.E = c->cfg.instances;
+    ap.t = trial_lines(c, 0, d_enc, d_lines, d_nlines);
+    ap.C = C;
+    ap.budget = max_nodes / ekf::ASSOC_W;
+    ap.bound = d_bound;
+    ap.cand = d_cand;
+    ap.hits = d_hits;
+    return enqueue_assoc(c, ap);
 }

@@ -5,26 +5,19 @@
 // stack into one innovation v (2m) with covariance S = H_J·P_J·H_Jᵀ + blockdiag(R) (2m × 2m); the
 // kernel reports vᵀS⁻¹v and log det S. One workgroup per (hypothesis, instance), one plain launch,
 // no cross-workgroup wait, no atomics: a hit depends on its own hypothesis and the state only.
-//   per line   (one thread per assigned line) the candidate exactly as the gate evaluates it
-//              (ekf_gate.h: eval_candidate, line_R, gate_predict, predict_cols; the landmark block by
-//              pll_block with the pending steps, then query_round): v, H, the diagonal 2×2 block of
-//              S with R, d2_each; and, shared through LDS, the predicted strip columns, H and
-//              G = H·P[:, 0:3] (innovation_cov's hp rows)
-//   per pair   (threads over the pairs a > b) the 2×2 block S_ab = G_a·A_bᵀ + Q_ab·B_bᵀ with
-//              Q_ab = A_a·C_b + B_a·D_ab, H = [A | B] on the columns {0, 1, 2 | l, l + 1}, C_b the strip
-//              columns of l_b and D_ab = P[l_a, l_b] read in its stored orientation. Every sum is
-//              written out in innovation_cov's order (for a = b it is that function's expression)
+//   per line   (one thread per assigned line) the candidate exactly as the gate evaluates it: v, the
+//              diagonal 2×2 block of S with R, d2_each; and, shared through LDS, the pairing's words
+//              (ekf_joint_parts.h: joint_line, which the joint-compatibility search shares)
+//   per pair   (threads over the pairs a > b) the 2×2 block S_ab (ekf_joint_parts.h: joint_pair)
 //   factor     S lower-only, packed by rows, in LDS (row r at r(r+1)/2), with v as row 2m behind it:
 //              right-looking Cholesky by columns, the trailing update on all threads. Element (r, c)
 //              takes its updates in ascending k whichever thread holds it, and row 2m comes out as
 //              z = L⁻¹v, so the forward solve is part of the factorisation. d2 = Σ z_k² and
 //              logdet = 2·Σ log L_kk, both summed by ascending k.
 // Packed storage: 2m = 128 takes 129·130/2 doubles = 65.5 KiB, so two workgroups share a CU's 160 KiB.
-#include "ekf_gate.h"
+#include "ekf_joint_parts.h"
 
 namespace ekf {
-
-enum { JL_H10 = 0, JL_H11, JL_H1L, JL_G = 3 /* [2][3] */, JL_C = 9 /* [3][2] */, JL_WORDS = 15 };
 
 __device__ __forceinline__ int tri(int r, int c) { return r * (r + 1) / 2 + c; }
 
@@ -85,30 +78,9 @@ __global__ __launch_bounds__(JOINT_THREADS) void joint_kernel(JointParams p)
     // ---- per line: the gate's candidate, the diagonal block, v ----
     if (tid < m) {
         const int a = tid, j = sh_lm[a], i = sh_li[a];
-        TrialRobot rb;
-        trial_robot(p.t, e, row, cm.Rs, d.n, rb);
-        TrialBlock tb;
-        trial_block<T>(pv, once, p.t.enc != nullptr, rb, cm, d.n, j, tb);
-        double sn, cs;
-        sincos(tb.yb.x, &sn, &cs);
-        const ekf_line ln = p.t.lines[(size_t)row * d.max_lines + i];
-        double Rm[4];
-        line_R(ln, i, p.t.r_mode, Rm);
         Cand c;
-        eval_candidate<true>(tb.b5, tb.yb.x, tb.yb.y, sn, cs, rb.xp, ln.alpha, ln.r, Rm, p.t.gate, gate_eta<T>(), c);
+        joint_line<T>(pv, once, p.t, cm, d, e, row, i, j, c, sh_ln[a]);
         if (each) each[i] = c.d2;
-        double S[4], hp0[5], hp1[5];
-        innovation_cov(tb.b5, c.h10, c.h11, c.h1l, Rm, S, hp0, hp1);   // (S == c.S; the hp rows are G)
-        double* w = sh_ln[a];
-        w[JL_H10] = c.h10; w[JL_H11] = c.h11; w[JL_H1L] = c.h1l;
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            w[JL_G + k] = hp0[k];
-            w[JL_G + 3 + k] = hp1[k];
-        }
-        w[JL_C + 0] = tb.rr0.x; w[JL_C + 1] = tb.rr0.y;
-        w[JL_C + 2] = tb.rr1.x; w[JL_C + 3] = tb.rr1.y;
-        w[JL_C + 4] = tb.rr2.x; w[JL_C + 5] = tb.rr2.y;
         // the lower half of the diagonal block (S[2], not S[1]) and the innovation
         A[tri(2 * a, 2 * a)] = c.S[0];
         A[tri(2 * a + 1, 2 * a)] = c.S[2];
@@ -125,24 +97,12 @@ __global__ __launch_bounds__(JOINT_THREADS) void joint_kernel(JointParams p)
         while (a * (a - 1) / 2 > q) a--;
         while ((a + 1) * a / 2 <= q) a++;
         const int b = q - a * (a - 1) / 2;   // 0 <= b < a < m
-        double Dab[4];
-        pll_block<T>(pv, 2 * sh_lm[a], 2 * sh_lm[b], Dab);   // P[l_a, l_b] (transposed on read if stored so)
-        query_round<T>(once, pv.ex, Dab);
-        const double* wa = sh_ln[a];
-        const double* wb = sh_ln[b];
-        const double h10 = wa[JL_H10], h11 = wa[JL_H11], h1l = wa[JL_H1L];
-        const double* C = wb + JL_C;   // P[k, l_b + c] at C[2k + c]
-        // Q_ab = H_a·P[:, l_b : l_b + 2] past the robot rows (innovation_cov's hp[3], hp[4])
-        const double q00 = -C[4] + Dab[0];
-        const double q01 = -C[5] + Dab[1];
-        const double q10 = h10 * C[0] + h11 * C[2] + h1l * Dab[0] + Dab[2];
-        const double q11 = h10 * C[1] + h11 * C[3] + h1l * Dab[1] + Dab[3];
-        const double* G = wa + JL_G;
-        const double g10 = wb[JL_H10], g11 = wb[JL_H11], g1l = wb[JL_H1L];
-        A[tri(2 * a, 2 * b)] = -G[2] + q00;
-        A[tri(2 * a, 2 * b + 1)] = G[0] * g10 + G[1] * g11 + q00 * g1l + q01;
-        A[tri(2 * a + 1, 2 * b)] = -G[5] + q10;
-        A[tri(2 * a + 1, 2 * b + 1)] = G[3] * g10 + G[4] * g11 + q10 * g1l + q11;
+        double Sab[4];
+        joint_pair<T>(pv, once, sh_lm[a], sh_lm[b], sh_ln[a], sh_ln[b], Sab);
+        A[tri(2 * a, 2 * b)] = Sab[0];
+        A[tri(2 * a, 2 * b + 1)] = Sab[1];
+        A[tri(2 * a + 1, 2 * b)] = Sab[2];
+        A[tri(2 * a + 1, 2 * b + 1)] = Sab[3];
     }
 
     // ---- Cholesky by columns with v as row n2: row n2 becomes z = L⁻¹v ----

@@ -44,6 +44,7 @@ EXPORTED = [
     "ekf_init_lowrank", "ekf_storage_exponent", "ekf_rescale", "ekf_get_pose_cov", "ekf_get_ellipse", "ekf_ellipse_of_block",
     "ekf_query_joint", "ekf_query_marginals", "ekf_query_joint_device",
     "ekf_gate_lines", "ekf_gate_lines_device", "ekf_gate_joint", "ekf_gate_joint_device",
+    "ekf_associate_joint", "ekf_associate_joint_device",
     "ekf_resample", "ekf_copy_instance",
     "ekf_instance_image_bytes", "ekf_export_instances", "ekf_import_instances",
     "ekf_export_instances_device", "ekf_import_instances_device",
@@ -101,6 +102,20 @@ class EkfJointHit(ctypes.Structure):
 
 
 ekf_joint_hit = EkfJointHit   # (the C name)
+
+ASSOC_MAX_CAND, ASSOC_MAX_LINES, ASSOC_MAX_TOTAL, ASSOC_MAX_NODES = 8, 16, 64, 1 << 22
+AS_TRUNCATED, AS_SINGULAR, AS_INVALID = 1, 2, 4   # ekf_assoc_hit.status
+
+
+class EkfAssocHit(ctypes.Structure):
+    """ekf_assoc_hit (slam_ekf.h): the best jointly compatible assignment of a scan's lines."""
+    _fields_ = [
+        ("m", ctypes.c_int32), ("status", ctypes.c_int32), ("nodes", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("d2", ctypes.c_double), ("logdet", ctypes.c_double), ("assign", ctypes.c_int32 * EKF_MAX_LINES),
+    ]
+
+
+ekf_assoc_hit = EkfAssocHit   # (the C name)
 
 
 class EkfImageDesc(ctypes.Structure):
@@ -174,6 +189,9 @@ def load_library(path: str = ""):
         "ekf_gate_lines_device": (ctypes.c_int, [vp, vp, vp, vp, vp, vp]),
         "ekf_gate_joint": (ctypes.c_int, [vp, ctypes.c_int, dp, vp, ctypes.c_int, vp, ctypes.c_int, vp, dp]),
         "ekf_gate_joint_device": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, vp, vp]),
+        "ekf_associate_joint": (ctypes.c_int, [vp, ctypes.c_int, dp, vp, ctypes.c_int, vp, ctypes.c_int, dp,
+                                               ctypes.c_int, vp]),
+        "ekf_associate_joint_device": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]),
         "ekf_resample": (ctypes.c_int, [vp, ip]),
         "ekf_copy_instance": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
         "ekf_instance_image_bytes": (sz, [vp]),
@@ -246,6 +264,52 @@ def ellipse_of_block(P22):
     if rc < 0:
         _check(-rc, "ekf_ellipse_of_block")
     return rc == 1, [axii[0], axii[1]], ang.value
+
+
+def gate_candidates(d2, C: int, gate: float) -> np.ndarray:
+    """The candidate lists ekf_associate_joint takes, from the individual distances d2 [L, N] of
+    ekf_gate_lines: per line the up to C landmarks with the smallest sqrt|d2| inside `gate`, ascending
+    (the lower landmark first on ties), padded with -1: [L, C] int32. Good children come first, so the
+    search's incumbent tightens early. NaN and +inf (at and past savedLineCount) are never candidates."""
+    d = np.sqrt(np.abs(np.asarray(d2, dtype=np.float64)))
+    d = d.reshape(-1, d.shape[-1]) if d.ndim else d.reshape(0, 0)
+    out = np.full((d.shape[0], int(C)), -1, dtype=np.int32)
+    for i, row in enumerate(d):
+        ok = np.flatnonzero(row <= gate)          # (NaN fails)
+        ok = ok[np.argsort(row[ok], kind="stable")][:C]
+        out[i, :len(ok)] = ok
+    return out
+
+
+def chi2_cdf_even(x: float, m: int) -> float:
+    """P(X <= x) for chi-square with 2m degrees of freedom: 1 - e^(-x/2) sum_{k<m} (x/2)^k / k!."""
+    h, term, acc = 0.5 * float(x), 1.0, 0.0
+    for k in range(int(m)):
+        acc += term
+        term *= h / (k + 1)
+    return 1.0 - float(np.exp(-h)) * acc
+
+
+def chi2_bounds(L: int, confidence: float) -> np.ndarray:
+    """bound[m], m = 0..L, for ekf_associate_joint: the chi-square quantile at `confidence` for 2m degrees
+    of freedom (bound[0] = 0), from the closed form for even degrees of freedom solved by bisection."""
+    if not 0.0 < confidence < 1.0:
+        raise ValueError("confidence must lie in (0, 1)")
+    out = np.zeros(int(L) + 1)
+    for m in range(1, int(L) + 1):
+        lo, hi = 0.0, 2.0 * m
+        while chi2_cdf_even(hi, m) < confidence:
+            hi *= 2.0
+        for _ in range(200):
+            mid = 0.5 * (lo + hi)
+            if mid == lo or mid == hi:
+                break
+            if chi2_cdf_even(mid, m) < confidence:
+                lo = mid
+            else:
+                hi = mid
+        out[m] = hi
+    return out
 
 
 def resample_plan(weights, u: float) -> list[int]:
@@ -525,6 +589,44 @@ class Ensemble:
                                                ctypes.c_void_p(d_hits or None), ctypes.c_void_p(d_d2_each or None)),
                "ekf_gate_joint_device")
 
+    def associate_joint(self, e: int, lines, cand, bound, encoder=None, max_nodes: int = 1 << 16):
+        """The joint-compatibility search against instance e's map, state untouched (slam_ekf.h
+        ekf_associate_joint): cand [L, C] int32, each line's candidate landmarks or -1 (gate_candidates);
+        bound [L + 1], the joint distance allowed with m pairings (chi2_bounds). Returns a dict (m, status,
+        nodes, d2, logdet, assign [L]): the jointly compatible assignment with the most pairings, then the
+        smallest d2; d2 and logdet are gate_joint's for `assign`, bit for bit. status carries AS_TRUNCATED
+        when max_nodes ran out (the result is then feasible but not guaranteed optimal) and AS_SINGULAR
+        when a child was pruned by a failed pivot. encoder as for gate_lines."""
+        la = np.ascontiguousarray(np.asarray(lines, dtype=np.float64).reshape(-1, 6))
+        L = int(la.shape[0])
+        ca = np.ascontiguousarray(np.asarray(cand, dtype=np.int32).reshape(L, -1) if L else np.zeros((0, 1), dtype=np.int32))
+        C = int(ca.shape[1])
+        ba = np.ascontiguousarray(np.asarray(bound, dtype=np.float64).reshape(-1))
+        if ba.shape[0] < L + 1:
+            raise ValueError("bound needs L + 1 entries")
+        enc = None if encoder is None else np.ascontiguousarray(np.asarray(encoder, dtype=np.float64).reshape(3))
+        hit = EkfAssocHit()
+        _check(self._lib.ekf_associate_joint(self._h, int(e), _dp(enc), la.ctypes.data_as(ctypes.c_void_p), L,
+                                             ca.ctypes.data_as(ctypes.c_void_p), C, _dp(ba), int(max_nodes),
+                                             ctypes.byref(hit)), "ekf_associate_joint")
+        return self._assoc_hit(hit, L)
+
+    @staticmethod
+    def _assoc_hit(h, L: int = EKF_MAX_LINES) -> dict:
+        return dict(m=h.m, status=h.status, nodes=h.nodes, d2=h.d2, logdet=h.logdet,
+                    assign=np.array(h.assign[:L], dtype=np.int32))
+
+    def associate_joint_device(self, d_enc: int, d_lines: int, d_nlines: int, d_cand: int, C: int, d_bound: int,
+                               d_hits: int, max_nodes: int = 1 << 16):
+        """The search of every instance at once, buffers in device memory (raw pointers: enc [E, 3] or 0,
+        lines [E, max_lines] ekf_line, nlines [E] int32, cand [E, max_lines, C] int32, bound
+        [max_lines + 1] shared by the instances, hits [E] ekf_assoc_hit); asynchronous on the context
+        stream."""
+        _check(self._lib.ekf_associate_joint_device(self._h, ctypes.c_void_p(d_enc or None), ctypes.c_void_p(d_lines or None),
+                                                    ctypes.c_void_p(d_nlines or None), ctypes.c_void_p(d_cand or None), int(C),
+                                                    ctypes.c_void_p(d_bound or None), int(max_nodes),
+                                                    ctypes.c_void_p(d_hits or None)), "ekf_associate_joint_device")
+
     def resample(self, src):
         """Instance e takes the whole state of instance src[e] on the device, pending steps included,
         without a drain or a flush (slam_ekf.h ekf_resample). Every source must keep its own state
@@ -739,6 +841,13 @@ class Robot:
         member). The state is untouched. See Ensemble.gate_joint."""
         rows, _ = self._as_rows(lines)
         return self._ens.gate_joint(0, rows, assign, encoder, each)
+
+    def associateJoint(self, lines, cand, bound, encoder=None, max_nodes: int = 1 << 16):
+        """The best jointly compatible assignment of the lines to their candidate landmarks (cand [L, C],
+        bound [L + 1]); the reference's association is first-fit and has no such member. The state is
+        untouched. See Ensemble.associate_joint."""
+        rows, _ = self._as_rows(lines)
+        return self._ens.associate_joint(0, rows, cand, bound, encoder, max_nodes)
 
     def getEllipse(self):
         ok, axii, angle = self._ens.ellipse(0)

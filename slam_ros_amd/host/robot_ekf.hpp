@@ -175,6 +175,24 @@ public:
         return ok;
     }
 
+    // The joint-compatibility search: cand holds, per line, C candidate landmarks or -1
+    // (cand.size() == C * lines.size()), bound[m] the joint distance allowed with m pairings
+    // (bound.size() == lines.size() + 1). hit is the jointly compatible assignment with the most
+    // pairings and, among those, the smallest joint distance (ekf_associate_joint); its d2 and logdet
+    // are gateJoint's for hit.assign. The state is untouched and the deferred flush is not drained.
+    // encoder as for gateLines.
+    bool associateJoint(const std::vector<Line>& lines, const std::vector<int32_t>& cand, const std::vector<double>& bound,
+                        ekf_assoc_hit& hit, const double* encoder = nullptr, int max_nodes = 1 << 16)
+    {
+        std::vector<ekf_line> buf;
+        if (!pack(lines, buf)) return false;
+        const size_t L = lines.size();
+        if (L == 0 || cand.size() % L || bound.size() != L + 1) return false;
+        return report(ekf_associate_joint(ctx_, 0, encoder, buf.data(), (int)L, cand.data(), (int)(cand.size() / L),
+                                          bound.data(), max_nodes, &hit),
+                      "ekf_associate_joint");
+    }
+
     void normalizeRadian(double& rad) { normalize_radian(rad); }
 
     void setMirror(Mirror m)
