@@ -1,7 +1,7 @@
-// ekf_api.hip — C-ABI (include/slam_ekf.h) over the gfx950 kernels (launchers: unit_*.hip): the context
-// (ekf_ctx.h), the schedule, scans and flushes, state upload / download, the partitioned instance. The
-// calls that leave the schedule as it is live beside it: ekf_read.hip (ekf_query_*, ekf_gate_lines*,
-// ekf_gate_joint*) and ekf_copy.hip (ekf_resample, ekf_copy_instance, the instance images).
+// ekf_api.hip — the core of the C-ABI (include/slam_ekf.h) over the gfx950 kernels (launchers: unit_*.hip):
+// the context's creation, options, the schedule of scans and flushes, results, profiling. A step's whole
+// host path is in this unit. The other host units (ekf_ctx.h lists them and what they share with this
+// one): ekf_state.hip, ekf_shard.hip, ekf_read.hip, ekf_copy.hip.
 //
 // A context owns E instances' state in HBM and two HIP streams:
 //   S  association/gain kernels (scan_kernel) — all state except the landmark block — and, on
@@ -25,12 +25,8 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include <dlfcn.h>
-
 #include <algorithm>
 #include <new>
-
-#include <rccl/rccl.h>   // (types only: the library loads RCCL on first use, ekf_rccl_unique_id)
 
 #include "ekf_ctx.h"
 
@@ -139,11 +135,9 @@ static void free_all(ekf_ctx* c)
     if (c->dstream) (void)hipStreamDestroy(c->dstream);
 }
 
-static int enqueue_flush(ekf_ctx* c);
-
 // Flush the partial group and wait for both streams; afterwards X[last_out] is the materialised
 // landmark block and nothing is pending.
-static int drain(ekf_ctx* c)
+int drain(ekf_ctx* c)
 {
     if (c->nsteps > c->unflushed0) {
         int rc = enqueue_flush(c);
@@ -157,17 +151,6 @@ static int drain(ekf_ctx* c)
     return EKF_OK;
 }
 
-// Every entry point that writes an instance's state without a scan (reset, upload, low-rank
-// initialisation, rescale, and any added later) starts here: the synchronous calls' result mirror
-// holds the robot block of the last scan, which the write makes stale (ekf_get_pose_cov must not
-// serve it), and the write needs the materialised landmark block.
-static int begin_state_write(ekf_ctx* c)
-{
-    c->mirror_epoch = 0;
-    c->predicted = 0;
-    return drain(c);
-}
-
 int end_read(ekf_ctx* c)
 {
     // Pipelined schedule: the next flush (a drain's, or the group's) writes X[base] on D, ordered
@@ -177,14 +160,8 @@ int end_read(ekf_ctx* c)
     return EKF_OK;
 }
 
-static inline int cur_buf(const ekf_ctx* c) { return c->last_out; }
-
-// instance e's stored tiles in buffer buf; and the kernels' view of instance 0, in which tile t sits
-// at t·TILE_ELEMS (a partitioned instance stores the tiles [t0, t1) only: the view is shifted)
-static inline char* xinst_ptr(const ekf_ctx* c, int buf, int e)
-{
-    return (char*)c->X[buf] + (size_t)e * c->xinst * c->elem;
-}
+// the kernels' view of instance 0 in buffer buf, in which tile t sits at t·TILE_ELEMS (a partitioned
+// instance stores the tiles [t0, t1) only: the view is shifted)
 void* xview(const ekf_ctx* c, int buf)
 {
     return (char*)c->X[buf] - (ptrdiff_t)c->t0 * ekf::TILE_ELEMS * (ptrdiff_t)c->elem;
@@ -192,7 +169,7 @@ void* xview(const ekf_ctx* c, int buf)
 
 // Committed copy of instance e's robot strip and mean (the association kernel flips it when it
 // commits a launch): read back after the stream has drained up to here.
-static int strip_copy(ekf_ctx* c, int e, int* cb)
+int strip_copy(ekf_ctx* c, int e, int* cb)
 {
     HIP_TRY(hipMemcpyAsync(cb, c->cur + e, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -200,94 +177,12 @@ static int strip_copy(ekf_ctx* c, int e, int* cb)
     return EKF_OK;
 }
 
-static inline double* strip_of(const ekf_ctx* c, int cb, int e)
-{
-    return c->Rs + ((size_t)cb * c->cfg.instances + e) * 3 * c->d.n;
-}
+// ---- create_ctx's steps, in the order it takes them. Each returns a status and leaves what it made on
+// the context's lists or in its named members, so one failure path (free_all) serves them all.
+#define ALLOC(ptr, bytes) do { if (!dev_alloc(c, (void**)&(ptr), (bytes))) return EKF_ENOMEM; } while (0)
 
-static inline double* mean_of(const ekf_ctx* c, int cb, int e)
+static int validate(const ekf_config* cfg, int* device)
 {
-    return c->y + ((size_t)cb * c->cfg.instances + e) * c->d.n;
-}
-
-static int set_exponent(ekf_ctx* c, int e, int ex)
-{
-    c->pexp_h[e] = ex;
-    HIP_TRY(hipMemcpy(c->pexp + e, &ex, sizeof(int), hipMemcpyHostToDevice));
-    return EKF_OK;
-}
-
-// fp16 storage exponent for a landmark block whose largest variance is vmax: the largest
-// 2^x <= 2^10 with 2^x·vmax <= 2^12 (16× below the fp16 range, 4× below the EKF_ST_RANGE warning)
-static int choose_exponent(const ekf_ctx* c, double vmax)
-{
-    if (c->cfg.precision != EKF_PREC_F16) return 0;
-    if (!(vmax > 0.0) || !std::isfinite(vmax)) return ekf::F16_EXP_DEFAULT;
-    const int x = (int)std::floor(std::log2(4096.0 / vmax));
-    return std::max(-24, std::min(ekf::F16_EXP_DEFAULT, x));
-}
-
-// EKF_ARITH_F16X3 plane exponent of instance e from its largest landmark variance (every context
-// keeps it; only F16X3 reads it)
-static int set_plane_scale(ekf_ctx* c, int e, double vmax)
-{
-    const int sg = ekf::plane_sigma(vmax);
-    const double vm = (vmax > 0.0 && std::isfinite(vmax)) ? vmax : 0.0;
-    HIP_TRY(hipMemcpy(c->psig + e, &sg, sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->pvmax + e, &vm, sizeof(double), hipMemcpyHostToDevice));
-    return EKF_OK;
-}
-
-static int set_robot_ctor(ekf_ctx* c, int e, double x, double y, double th)
-{
-    // Robot::Robot (Robot.cpp:20-35): P_t0[0][0] = P_t0[1][1] = 0.05, P_t0[2][2] = 0, the rest
-    // (and y, savedLineCount) zero.
-    const Dims& d = c->d;
-    HIP_TRY(hipMemsetAsync(xinst_ptr(c, cur_buf(c), e), 0, c->xinst * c->elem, c->stream));
-    const int zero = 0;
-    const double v = 0.05;
-    HIP_TRY(hipMemcpyAsync(c->cur + e, &zero, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    for (int cb = 0; cb < 2; cb++) {
-        HIP_TRY(hipMemsetAsync(strip_of(c, cb, e), 0, sizeof(double) * 3 * d.n, c->stream));
-        HIP_TRY(hipMemsetAsync(mean_of(c, cb, e), 0, sizeof(double) * d.n, c->stream));
-        HIP_TRY(hipMemcpyAsync(strip_of(c, cb, e) + 0, &v, sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(strip_of(c, cb, e) + d.n + 1, &v, sizeof(double), hipMemcpyHostToDevice,
-                               c->stream));
-    }
-    const double pose[3] = {x, y, th};
-    HIP_TRY(hipMemcpyAsync(c->pose + 3 * e, pose, sizeof(pose), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->xpre + 3 * e, pose, sizeof(pose), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->saved + e, &zero, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const int rc = set_plane_scale(c, e, 0.0);   // an empty map
-    if (rc) return rc;
-    return set_exponent(c, e, c->cfg.precision == EKF_PREC_F16 ? ekf::F16_EXP_DEFAULT : 0);
-}
-
-static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx** out);
-
-extern "C" int ekf_create(const ekf_config* cfg, ekf_ctx** out)
-{
-    return create_ctx(cfg, -1, 0, out);
-}
-
-extern "C" int ekf_shard_create(const ekf_config* cfg, int rank, int world, ekf_ctx** out)
-{
-    if (!cfg || !out) return EKF_EINVAL;
-    *out = nullptr;
-    // one instance, the exact arithmetic, fp32 or fp64 storage, the sequential schedule, groups the
-    // wave flushes take (fp32 <= 8 steps, fp64 <= 8)
-    if (world < 1 || rank < 0 || rank >= world || cfg->instances != 1 || cfg->pipeline ||
-        cfg->arith != EKF_ARITH_EXACT || (cfg->precision != EKF_PREC_F32 && cfg->precision != EKF_PREC_F64) ||
-        cfg->flush_interval > (cfg->precision == EKF_PREC_F64 ? ekf::F64_WAVE_MAXS : 8) || cfg->max_lines > 8)
-        return EKF_EINVAL;
-    return create_ctx(cfg, rank, world, out);
-}
-
-static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx** out)
-{
-    if (!cfg || !out) return EKF_EINVAL;
-    *out = nullptr;
     // capacity bound: one association thread per landmark, at most MAX_GROUPS workgroups of
     // SCAN_THREADS per instance (N <= 32768, i.e. n <= 65539)
     if (cfg->capacity < 1 || cfg->capacity > ekf::MAX_CAPACITY ||
@@ -306,30 +201,24 @@ static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx*
         return EKF_EINVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return EKF_EDEVICE;
-    ekf_ctx* c = new (std::nothrow) ekf_ctx();
-    if (!c) return EKF_ENOMEM;
-    c->cfg = *cfg;
-    if (cfg->device >= 0) {
-        if (cfg->device >= ndev || hipSetDevice(cfg->device) != hipSuccess) {
-            delete c;
-            return EKF_EDEVICE;
-        }
-    }
-    (void)hipGetDevice(&c->device);
-    c->d = ekf::make_dims(cfg->capacity, cfg->max_lines);
+    if (cfg->device >= 0 && (cfg->device >= ndev || hipSetDevice(cfg->device) != hipSuccess)) return EKF_EDEVICE;
+    (void)hipGetDevice(device);
+    return EKF_OK;
+}
+
+// sizes, the rank's tiles, the association grid
+static int set_dims(ekf_ctx* c, int sh_rank, int sh_world)
+{
+    const ekf_config& cfg = c->cfg;
+    c->d = ekf::make_dims(cfg.capacity, cfg.max_lines);
     const Dims& d = c->d;
-    const int E = cfg->instances;
-    c->elem = (cfg->precision == EKF_PREC_F64) ? 8 : (cfg->precision == EKF_PREC_F32) ? 4 : 2;
-    c->op_elem = (cfg->precision == EKF_PREC_F64) ? 8 : 4;   // operands in the compute type
+    c->elem = (cfg.precision == EKF_PREC_F64) ? 8 : (cfg.precision == EKF_PREC_F32) ? 4 : 2;
+    c->op_elem = (cfg.precision == EKF_PREC_F64) ? 8 : 4;   // operands in the compute type
     c->pll_inst = (size_t)d.ntiles * ekf::TILE_ELEMS;
-    c->t0 = 0;
     c->t1 = d.ntiles;
     if (sh_world > 0) {
         ekf::tile_partition(d.nb, sh_world, sh_rank, c->sh_r0, c->sh_r1);
-        if (c->sh_r0 >= c->sh_r1) {   // more ranks than wave-tile rows
-            delete c;
-            return EKF_ERANGE;
-        }
+        if (c->sh_r0 >= c->sh_r1) return EKF_ERANGE;   // more ranks than wave-tile rows
         c->sh_rank = sh_rank;
         c->sh_world = sh_world;
         c->t0 = ekf::tile_index(c->sh_r0, c->sh_r0, d.nb);
@@ -340,16 +229,19 @@ static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx*
     c->G = (d.N + ekf::SCAN_THREADS - 1) / ekf::SCAN_THREADS;
     c->Gmax = (d.N + 63) / 64;   // EKF_OPT_SCAN_THREADS = 64
     c->last_G = c->G;
-    c->nt_opt = 0;
     // pipeline: the association kernels of an instance spread over G > 1 cooperating workgroups
     // must never wait on CUs a flush holds, so they are ordered after the flush in flight, and
     // nothing would overlap: such contexts run the sequential schedule (slam_ekf.h)
     if (c->G > 1) c->cfg.pipeline = 0;
-    int rc = EKF_ENOMEM;
-#define ALLOC(ptr, bytes) do { if (!dev_alloc(c, (void**)&(ptr), (bytes))) goto fail; } while (0)
+    return EKF_OK;
+}
+
+static int make_state(ekf_ctx* c)
+{
+    const Dims& d = c->d;
+    const int E = c->cfg.instances;
     ALLOC(c->X[0], c->xinst * c->elem * E);
     if (c->cfg.pipeline) ALLOC(c->X[1], c->xinst * c->elem * E);
-    else c->X[1] = nullptr;
     ALLOC(c->Rs, sizeof(double) * 3 * d.n * E * 2);
     ALLOC(c->y, sizeof(double) * d.n * E * 2);
     ALLOC(c->cur, sizeof(int) * E);
@@ -359,7 +251,15 @@ static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx*
     ALLOC(c->D, sizeof(double) * 4 * d.N * E * 2);
     ALLOC(c->Ust, sizeof(double) * d.max_lines * d.n * 2 * E);
     ALLOC(c->Vst, sizeof(double) * d.max_lines * d.n * 2 * E);
-    c->T = cfg->flush_interval > 0 ? cfg->flush_interval : 1;
+    return EKF_OK;
+}
+
+// the ring of per-step slots and their operand buffers
+static int make_ring(ekf_ctx* c)
+{
+    const Dims& d = c->d;
+    const int E = c->cfg.instances;
+    c->T = c->cfg.flush_interval > 0 ? c->cfg.flush_interval : 1;
     c->ring.assign((size_t)c->T * (c->cfg.pipeline ? 2 : 1), ekf::Slot{});
     // the operand rows of all slots in two contiguous buffers (fixed slot stride): the wave
     // flush addresses step q's rows from one base and its ring index (DowndateParams::ubase)
@@ -368,10 +268,8 @@ static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx*
     ALLOC(c->ops_v, (size_t)c->slot_bytes * c->ring.size());
     // split-plane flushes: V's planes per slot (written by the association kernel), three bf16
     // (BF16X6) or two fp16 (F16X3) per operand element
-    c->bf = cfg->arith != EKF_ARITH_EXACT;   // (validated above: fp32 / fp16, symmetric R, kmax 16)
-    c->pmode = c->bf ? cfg->arith : 0;
-    c->ops_b = nullptr;
-    c->bslot_bytes = 0;
+    c->bf = c->cfg.arith != EKF_ARITH_EXACT;   // (validated: fp32 / fp16, symmetric R, kmax 16)
+    c->pmode = c->bf ? c->cfg.arith : 0;
     if (c->bf) {
         const int npl = c->pmode == EKF_ARITH_F16X3 ? 2 : 3;
         c->bslot_bytes = (long long)((c->op_inst * npl * 2 * E + 255) / 256 * 256);
@@ -388,20 +286,32 @@ static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx*
         ALLOC(sl.patch_diag, sizeof(double) * d.max_lines * 4 * E);
         ALLOC(sl.res, sizeof(int) * ekf::RES_STRIDE * E);
     }
-    {
-        // the flush kernels' tile tables (ekf_tables.h). A partitioned instance flushes its tile rows
-        // only: its wave tables keep those rows, and it has no quad table
-        const bool part = c->sh_world > 0;
-        const auto wt = ekf::wt_table(d.nb), wt64 = ekf::wt64_table(d.nb);
-        if (!upload_table(c, &c->tile_rc, ekf::tile_rc_table(d.nb)) ||
-            !upload_table(c, &c->stile_rc, ekf::stile_rc_table(d.nb)) ||
-            !upload_table(c, &c->stile2_rc, ekf::stile2_rc_table(d.nb), &c->nstiles2) ||
-            !upload_table(c, &c->wt, part ? ekf::keep_tile_rows(wt, ekf::WT_R, c->sh_r0, c->sh_r1) : wt, &c->nwt) ||
-            !upload_table(c, &c->wt64, part ? ekf::keep_tile_rows(wt64, 1, c->sh_r0, c->sh_r1) : wt64, &c->nwt64) ||
-            !upload_table(c, &c->wt24, ekf::wt24_table(d.nb), &c->nwt24) ||
-            (!part && !upload_table(c, &c->wtq, ekf::wtq_table(d.nb), &c->nwtq)))
-            goto fail;
-    }
+    return EKF_OK;
+}
+
+// the flush kernels' tile tables (ekf_tables.h). A partitioned instance flushes its tile rows
+// only: its wave tables keep those rows, and it has no quad table
+static int make_tables(ekf_ctx* c)
+{
+    const Dims& d = c->d;
+    const bool part = c->sh_world > 0;
+    const auto wt = ekf::wt_table(d.nb), wt64 = ekf::wt64_table(d.nb);
+    if (!upload_table(c, &c->tile_rc, ekf::tile_rc_table(d.nb)) ||
+        !upload_table(c, &c->stile_rc, ekf::stile_rc_table(d.nb)) ||
+        !upload_table(c, &c->stile2_rc, ekf::stile2_rc_table(d.nb), &c->nstiles2) ||
+        !upload_table(c, &c->wt, part ? ekf::keep_tile_rows(wt, ekf::WT_R, c->sh_r0, c->sh_r1) : wt, &c->nwt) ||
+        !upload_table(c, &c->wt64, part ? ekf::keep_tile_rows(wt64, 1, c->sh_r0, c->sh_r1) : wt64, &c->nwt64) ||
+        !upload_table(c, &c->wt24, ekf::wt24_table(d.nb), &c->nwt24) ||
+        (!part && !upload_table(c, &c->wtq, ekf::wtq_table(d.nb), &c->nwtq)))
+        return EKF_ENOMEM;
+    return EKF_OK;
+}
+
+// the scan's device inputs, its mailbox, and the options' defaults
+static int make_scan_buffers(ekf_ctx* c)
+{
+    const Dims& d = c->d;
+    const int E = c->cfg.instances;
     c->in_lines = ((sizeof(double) * 3 * E + 15) / 16) * 16;
     c->in_nlines = c->in_lines + ((sizeof(ekf_line) * d.max_lines * E + 15) / 16) * 16;
     c->in_bytes = c->in_nlines + sizeof(int) * E;
@@ -422,97 +332,144 @@ static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx*
     c->mfrep_opt = 1;
     c->active_flush = 1;
     c->mfrep = c->bf ? 1 : 0;
-    c->dbg = nullptr;
     ALLOC(c->mbox, sizeof(double) * 2 * c->Gmax * c->mbw * E);
-    if (c->sh_world > 0) {
-        // the partitioned instance's scan state (replicated on every rank) and a step that applies
-        // nothing (rolled back: every flush form skips it), which pads an odd partial group
-        ALLOC(c->sh_rob, sizeof(double) * 12);
-        ALLOC(c->sh_rec, sizeof(double) * d.N * ekf::SH_REC);
-        ALLOC(c->sh_hist, sizeof(double) * d.N * d.max_lines * 8);
-        ALLOC(c->sh_pkg, sizeof(double) * (ekf::MB_WORDS_FIXED + 4 * d.max_lines));
-        ALLOC(c->sh_flags, sizeof(int) * d.N);
-        ALLOC(c->sh_ctl, sizeof(int) * ekf::SC_WORDS);
-        ALLOC(c->sh_null.res, sizeof(int) * ekf::RES_STRIDE);
-        const int one = 1;
-        if (hipMemcpy(c->sh_null.res + ekf::RES_ROLLBACK, &one, sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-            goto fail;
-        c->sh_null.Uop = c->ring[0].Uop;
-        c->sh_null.Vop = c->ring[0].Vop;
-        c->sh_null.patch = c->ring[0].patch;
-        c->sh_null.patch_diag = c->ring[0].patch_diag;
-    }
+    return EKF_OK;
+}
+
+// the partitioned instance's scan state (replicated on every rank) and a step that applies
+// nothing (rolled back: every flush form skips it), which pads an odd partial group
+static int make_shard_buffers(ekf_ctx* c)
+{
+    if (c->sh_world <= 0) return EKF_OK;
+    const Dims& d = c->d;
+    ALLOC(c->sh_rob, sizeof(double) * 12);
+    ALLOC(c->sh_rec, sizeof(double) * d.N * ekf::SH_REC);
+    ALLOC(c->sh_hist, sizeof(double) * d.N * d.max_lines * 8);
+    ALLOC(c->sh_pkg, sizeof(double) * (ekf::MB_WORDS_FIXED + 4 * d.max_lines));
+    ALLOC(c->sh_flags, sizeof(int) * d.N);
+    ALLOC(c->sh_ctl, sizeof(int) * ekf::SC_WORDS);
+    ALLOC(c->sh_null.res, sizeof(int) * ekf::RES_STRIDE);
+    const int one = 1;
+    if (hipMemcpy(c->sh_null.res + ekf::RES_ROLLBACK, &one, sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+        return EKF_ENOMEM;
+    c->sh_null.Uop = c->ring[0].Uop;
+    c->sh_null.Vop = c->ring[0].Vop;
+    c->sh_null.patch = c->ring[0].patch;
+    c->sh_null.patch_diag = c->ring[0].patch_diag;
+    return EKF_OK;
+}
+
+// what the results are read from: the workgroups' completion words, the pinned records and the
+// synchronous calls' mirror with their device pointers; and the pinned input staging
+static int make_host_buffers(ekf_ctx* c)
+{
+    const int E = c->cfg.instances;
     c->sync_stride = ((ekf::SYNC_WG0 + c->Gmax + 15) / 16) * 16;
     ALLOC(c->sync, sizeof(int) * c->sync_stride * E);
-#undef ALLOC
     if (!pinned_alloc(c, (void**)&c->h_res, sizeof(int) * ekf::RES_STRIDE * E) ||
         !pinned_alloc(c, (void**)&c->h_pose, sizeof(double) * 3 * E) ||
         !pinned_alloc(c, (void**)&c->h_r33, sizeof(double) * 9 * E) ||
         !pinned_alloc(c, (void**)&c->h_ep, sizeof(unsigned) * E) ||
-        !pinned_alloc(c, (void**)&c->h_in, c->in_bytes))
-        goto fail;
-    if (hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming) != hipSuccess) goto fail;
-    memset(c->h_ep, 0, sizeof(unsigned) * E);
-    if (hipHostGetDevicePointer((void**)&c->hd_res, c->h_res, 0) != hipSuccess ||
+        !pinned_alloc(c, (void**)&c->h_in, c->in_bytes) ||
+        hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming) != hipSuccess ||
+        hipHostGetDevicePointer((void**)&c->hd_res, c->h_res, 0) != hipSuccess ||
         hipHostGetDevicePointer((void**)&c->hd_pose, c->h_pose, 0) != hipSuccess ||
         hipHostGetDevicePointer((void**)&c->hd_r33, c->h_r33, 0) != hipSuccess ||
         hipHostGetDevicePointer((void**)&c->hd_ep, c->h_ep, 0) != hipSuccess)
-        goto fail;
-    rc = EKF_EDEVICE;
-    if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) goto fail;
-    if (hipStreamCreateWithFlags(&c->dstream, hipStreamNonBlocking) != hipSuccess) goto fail;
-    c->stream = c->own_stream;
-    if (hipEventCreateWithFlags(&c->ev_scan, hipEventDisableTiming) != hipSuccess) goto fail;
-    for (int k = 0; k < 2; k++)
-        if (hipEventCreateWithFlags(&c->ev_flush[k], hipEventDisableTiming) != hipSuccess) goto fail;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) goto fail;
-        c->dd_per_cu = 8;   // downdate workgroups per CU (4 waves each; EKF_OPT_FLUSH_BLOCKS_PER_CU)
-        c->dd_grid = prop.multiProcessorCount * c->dd_per_cu;
-        c->ncu = prop.multiProcessorCount;
-        // automatic flush form (EKF_OPT_FLUSH_FORM); a partitioned instance: the wave form for every
-        // group (its wave tables hold the rank's tile rows only; the other forms walk every tile)
-        c->dd_variant = c->sh_world > 0 ? ekf::FORM_WAVE : ekf::FORM_AUTO;
-        // all G workgroups of an instance must be co-resident (they exchange per line). A plain
-        // launch gets the same residency as a cooperative one for the same grid
-        // (cdna_hip_programming.md §1; the cooperative form only adds a launch-time check of the
-        // same occupancy query, which can over-report, for ≈17 µs per launch), so the grid is
-        // sized from a bound that cannot over-report: the LDS the kernel declares (one block per
-        // CU at 128 KB of 160 KB), capped by the occupancy query less one block of margin when
-        // the query allows more than one.
-        int per_cu = ekf::scan_blocks_per_cu(cfg->precision);
-        if (per_cu > 1) per_cu -= 1;
-        const size_t lds = ekf::scan_lds_bytes(cfg->precision);
-        if (lds > 0 && prop.maxSharedMemoryPerMultiProcessor > 0) {
-            const int by_lds = (int)(prop.maxSharedMemoryPerMultiProcessor / lds);
-            if (by_lds < per_cu) per_cu = by_lds;
-        }
-        if (per_cu < 1) {
-            rc = EKF_EINVAL;
-            goto fail;
-        }
-        const int resident = prop.multiProcessorCount * per_cu;
-        c->resident = resident;
-        c->scan_batch = resident / c->G;
-        if (c->scan_batch < 1) {
-            rc = EKF_EINVAL;   // one instance does not fit the device
-            goto fail;
-        }
-        if (c->scan_batch > E) c->scan_batch = E;
-    }
-    c->base = c->last_out = 0;
-    for (int e = 0; e < E; e++)
-        if (set_robot_ctor(c, e, 0.0, 0.0, 0.0) != EKF_OK) goto fail;
-    *out = c;
+        return EKF_ENOMEM;
+    memset(c->h_ep, 0, sizeof(unsigned) * E);
     return EKF_OK;
-fail:
-    free_all(c);
-    delete c;
-    return rc;
+}
+#undef ALLOC
+
+static int make_streams(ekf_ctx* c)
+{
+    if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
+        hipStreamCreateWithFlags(&c->dstream, hipStreamNonBlocking) != hipSuccess)
+        return EKF_EDEVICE;
+    c->stream = c->own_stream;
+    if (hipEventCreateWithFlags(&c->ev_scan, hipEventDisableTiming) != hipSuccess) return EKF_EDEVICE;
+    for (int k = 0; k < 2; k++)
+        if (hipEventCreateWithFlags(&c->ev_flush[k], hipEventDisableTiming) != hipSuccess) return EKF_EDEVICE;
+    return EKF_OK;
 }
 
-static void rccl_destroy(ekf_ctx* c);
+// the flush grid and how many instances one association launch takes
+static int size_launches(ekf_ctx* c)
+{
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) return EKF_EDEVICE;
+    c->dd_per_cu = 8;   // downdate workgroups per CU (4 waves each; EKF_OPT_FLUSH_BLOCKS_PER_CU)
+    c->dd_grid = prop.multiProcessorCount * c->dd_per_cu;
+    c->ncu = prop.multiProcessorCount;
+    // automatic flush form (EKF_OPT_FLUSH_FORM); a partitioned instance: the wave form for every
+    // group (its wave tables hold the rank's tile rows only; the other forms walk every tile)
+    c->dd_variant = c->sh_world > 0 ? ekf::FORM_WAVE : ekf::FORM_AUTO;
+    // all G workgroups of an instance must be co-resident (they exchange per line). A plain
+    // launch gets the same residency as a cooperative one for the same grid
+    // (cdna_hip_programming.md §1; the cooperative form only adds a launch-time check of the
+    // same occupancy query, which can over-report, for ≈17 µs per launch), so the grid is
+    // sized from a bound that cannot over-report: the LDS the kernel declares (one block per
+    // CU at 128 KB of 160 KB), capped by the occupancy query less one block of margin when
+    // the query allows more than one.
+    int per_cu = ekf::scan_blocks_per_cu(c->cfg.precision);
+    if (per_cu > 1) per_cu -= 1;
+    const size_t lds = ekf::scan_lds_bytes(c->cfg.precision);
+    if (lds > 0 && prop.maxSharedMemoryPerMultiProcessor > 0) {
+        const int by_lds = (int)(prop.maxSharedMemoryPerMultiProcessor / lds);
+        if (by_lds < per_cu) per_cu = by_lds;
+    }
+    if (per_cu < 1) return EKF_EINVAL;
+    c->resident = prop.multiProcessorCount * per_cu;
+    c->scan_batch = c->resident / c->G;
+    if (c->scan_batch < 1) return EKF_EINVAL;   // one instance does not fit the device
+    if (c->scan_batch > c->cfg.instances) c->scan_batch = c->cfg.instances;
+    return EKF_OK;
+}
+
+static int create_ctx(const ekf_config* cfg, int sh_rank, int sh_world, ekf_ctx** out)
+{
+    if (!cfg || !out) return EKF_EINVAL;
+    *out = nullptr;
+    int device = 0;
+    int rc = validate(cfg, &device);
+    if (rc) return rc;
+    ekf_ctx* c = new (std::nothrow) ekf_ctx();   // (zeroed: the steps set what is not zero or null)
+    if (!c) return EKF_ENOMEM;
+    c->cfg = *cfg;
+    c->device = device;
+    static int (*const steps[])(ekf_ctx*) = {make_state, make_ring, make_tables, make_scan_buffers,
+                                             make_shard_buffers, make_host_buffers, make_streams, size_launches};
+    rc = set_dims(c, sh_rank, sh_world);
+    for (auto step : steps)
+        if (!rc) rc = step(c);
+    for (int e = 0; !rc && e < cfg->instances; e++) rc = set_robot_ctor(c, e, 0.0, 0.0, 0.0);
+    if (rc) {
+        free_all(c);
+        delete c;
+        return rc;
+    }
+    *out = c;
+    return EKF_OK;
+}
+
+extern "C" int ekf_create(const ekf_config* cfg, ekf_ctx** out)
+{
+    return create_ctx(cfg, -1, 0, out);
+}
+
+extern "C" int ekf_shard_create(const ekf_config* cfg, int rank, int world, ekf_ctx** out)
+{
+    if (!cfg || !out) return EKF_EINVAL;
+    *out = nullptr;
+    // one instance, the exact arithmetic, fp32 or fp64 storage, the sequential schedule, groups the
+    // wave flushes take (fp32 <= 8 steps, fp64 <= 8)
+    if (world < 1 || rank < 0 || rank >= world || cfg->instances != 1 || cfg->pipeline ||
+        cfg->arith != EKF_ARITH_EXACT || (cfg->precision != EKF_PREC_F32 && cfg->precision != EKF_PREC_F64) ||
+        cfg->flush_interval > (cfg->precision == EKF_PREC_F64 ? ekf::F64_WAVE_MAXS : 8) || cfg->max_lines > 8)
+        return EKF_EINVAL;
+    return create_ctx(cfg, rank, world, out);
+}
 
 extern "C" int ekf_destroy(ekf_ctx* c)
 {
@@ -614,22 +571,6 @@ extern "C" int ekf_get_option(const ekf_ctx* c, int opt, int* v)
     default: return EKF_EINVAL;
     }
     return EKF_OK;
-}
-
-extern "C" int ekf_reset_instance(ekf_ctx* c, int e, double x, double y, double th)
-{
-    if (!c) return EKF_EINVAL;
-    if (e >= c->cfg.instances) return EKF_ERANGE;
-    int rc = begin_state_write(c);
-    if (rc) return rc;
-    if (e < 0) {
-        for (int k = 0; k < c->cfg.instances; k++) {
-            rc = set_robot_ctor(c, k, x, y, th);
-            if (rc) return rc;
-        }
-        return EKF_OK;
-    }
-    return set_robot_ctor(c, e, x, y, th);
 }
 
 // profiling level 1 times the flush only (what the roofline needs, 2 events per group);
@@ -765,7 +706,7 @@ static ekf::FlushPlan flush_plan_of(const ekf_ctx* c, int nsteps)
 }
 
 // One pass over the landmark block applying steps [unflushed0, nsteps) (stream D).
-static int enqueue_flush(ekf_ctx* c)
+int enqueue_flush(ekf_ctx* c)
 {
     const int nst = (int)(c->nsteps - c->unflushed0);
     if (nst <= 0) return EKF_OK;
@@ -906,8 +847,6 @@ static int stage_inputs(ekf_ctx* c, const double* enc, const ekf_line* lines, co
     return EKF_OK;
 }
 
-static void fill_results(const ekf_ctx* c, ekf_result* out);
-
 extern "C" int ekf_read_results(ekf_ctx* c, ekf_result* out)
 {
     if (!c) return EKF_EINVAL;
@@ -942,7 +881,7 @@ extern "C" int ekf_read_results(ekf_ctx* c, ekf_result* out)
 }
 
 // ekf_result of every instance from the host copies of the last step's records and poses
-static void fill_results(const ekf_ctx* c, ekf_result* out)
+void fill_results(const ekf_ctx* c, ekf_result* out)
 {
     const int E = c->cfg.instances;
     if (!out) return;
@@ -1017,788 +956,6 @@ extern "C" int ekf_update(ekf_ctx* c, const ekf_line* lines, const int32_t* nlin
     int rc = stage_inputs(c, nullptr, lines, nlines);
     if (rc) return rc;
     return enqueue_mirrored(c, ekf::PHASE_UPDATE, out);
-}
-
-// The dense n × n fp64 scratch of the state transfers: allocated on first use and kept, so that a
-// caller mirroring P after every scan (the drop-in's full mirror) does not allocate per call
-static hipError_t dense_scratch(ekf_ctx* c, double** out)
-{
-    if (!c->dense) {
-        const hipError_t err = hipMalloc((void**)&c->dense, sizeof(double) * c->d.n * c->d.n);
-        if (err != hipSuccess) {
-            c->dense = nullptr;
-            return err;
-        }
-    }
-    *out = c->dense;
-    return hipSuccess;
-}
-
-extern "C" int ekf_upload_state(ekf_ctx* c, int e, const double* P, const double* y, int saved,
-                                const double pose[3])
-{
-    if (!c) return EKF_EINVAL;
-    if (e < 0 || e >= c->cfg.instances) return EKF_ERANGE;
-    if (saved < 0 || saved > c->d.N) return EKF_ERANGE;
-    int rc = begin_state_write(c);
-    if (rc) return rc;
-    const Dims& d = c->d;
-    int cb = 0;
-    rc = strip_copy(c, e, &cb);
-    if (rc) return rc;
-    if (P) {
-        double vmax = 0.0;
-        for (int i = 3; i < d.n; i++) vmax = std::max(vmax, std::fabs(P[(size_t)i * d.n + i]));
-        rc = set_exponent(c, e, choose_exponent(c, vmax));
-        if (rc) return rc;
-        rc = set_plane_scale(c, e, vmax);
-        if (rc) return rc;
-        double* tmp = nullptr;
-        HIP_TRY(dense_scratch(c, &tmp));
-        hipError_t err = hipMemcpyAsync(tmp, P, sizeof(double) * d.n * d.n, hipMemcpyHostToDevice,
-                                        c->stream);
-        if (err == hipSuccess)
-            err = ekf::launch_pack(d, c->cfg.precision, tmp, xinst_ptr(c, cur_buf(c), e),
-                                   strip_of(c, cb, e), c->tile_rc, c->pexp_h[e], c->stream, c->t0, c->t1);
-        if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-        HIP_TRY(err);
-    }
-    if (y)
-        HIP_TRY(hipMemcpyAsync(mean_of(c, cb, e), y, sizeof(double) * d.n,
-                               hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->saved + e, &saved, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    if (pose) {
-        HIP_TRY(hipMemcpyAsync(c->pose + 3 * e, pose, sizeof(double) * 3, hipMemcpyHostToDevice,
-                               c->stream));
-        HIP_TRY(hipMemcpyAsync(c->xpre + 3 * e, pose, sizeof(double) * 3, hipMemcpyHostToDevice,
-                               c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return EKF_OK;
-}
-
-extern "C" int ekf_download_state(ekf_ctx* c, int e, double* P, double* y, int* saved,
-                                  double pose[3])
-{
-    if (!c) return EKF_EINVAL;
-    if (e < 0 || e >= c->cfg.instances) return EKF_ERANGE;
-    // P drains (the pending downdates are flushed first); the mean, pose and savedLineCount are
-    // committed by every association kernel, so without P the call only waits for the stream and
-    // leaves the flush schedule as it is
-    int rc = EKF_OK;
-    if (P) rc = drain(c);
-    else HIP_TRY(hipStreamSynchronize(c->stream));
-    if (rc) return rc;
-    const Dims& d = c->d;
-    int cb = 0;
-    rc = strip_copy(c, e, &cb);
-    if (rc) return rc;
-    if (P) {
-        double* tmp = nullptr;
-        HIP_TRY(dense_scratch(c, &tmp));
-        hipError_t err = ekf::launch_unpack(d, c->cfg.precision, tmp, xinst_ptr(c, cur_buf(c), e),
-                                            strip_of(c, cb, e), c->pexp_h[e], c->stream, c->t0, c->t1);
-        if (err == hipSuccess)
-            err = hipMemcpyAsync(P, tmp, sizeof(double) * d.n * d.n, hipMemcpyDeviceToHost,
-                                 c->stream);
-        if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-        HIP_TRY(err);
-    }
-    if (y)
-        HIP_TRY(hipMemcpyAsync(y, mean_of(c, cb, e), sizeof(double) * d.n,
-                               hipMemcpyDeviceToHost, c->stream));
-    if (saved)
-        HIP_TRY(hipMemcpyAsync(saved, c->saved + e, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (pose)
-        HIP_TRY(hipMemcpyAsync(pose, c->pose + 3 * e, sizeof(double) * 3, hipMemcpyDeviceToHost,
-                               c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return EKF_OK;
-}
-
-extern "C" int ekf_init_lowrank(ekf_ctx* c, int e, const double* diag, const double* U, int rank,
-                                const double* y, int saved, const double pose[3])
-{
-    if (!c || !diag || (rank > 0 && !U) || rank < 0) return EKF_EINVAL;
-    if (e < 0 || e >= c->cfg.instances) return EKF_ERANGE;
-    int rc = begin_state_write(c);
-    if (rc) return rc;
-    const Dims& d = c->d;
-    int cb = 0;
-    rc = strip_copy(c, e, &cb);
-    if (rc) return rc;
-    double vmax = 0.0;
-    for (int i = 3; i < d.n; i++) {
-        double v = diag[i];
-        for (int k = 0; k < rank; k++) v += U[(size_t)i * rank + k] * U[(size_t)i * rank + k];
-        vmax = std::max(vmax, std::fabs(v));
-    }
-    rc = set_exponent(c, e, choose_exponent(c, vmax));
-    if (rc) return rc;
-    rc = set_plane_scale(c, e, vmax);
-    if (rc) return rc;
-    double *dd = nullptr, *du = nullptr;
-    HIP_TRY(hipMalloc((void**)&dd, sizeof(double) * d.n));
-    hipError_t err = hipMalloc((void**)&du, sizeof(double) * d.n * (rank > 0 ? rank : 1));
-    if (err == hipSuccess)
-        err = hipMemcpyAsync(dd, diag, sizeof(double) * d.n, hipMemcpyHostToDevice, c->stream);
-    if (err == hipSuccess && rank > 0)
-        err = hipMemcpyAsync(du, U, sizeof(double) * d.n * rank, hipMemcpyHostToDevice, c->stream);
-    if (err == hipSuccess)
-        err = ekf::launch_lowrank(d, c->cfg.precision, dd, du, rank, xinst_ptr(c, cur_buf(c), e),
-                                  strip_of(c, cb, e), c->tile_rc, c->pexp_h[e], c->stream, c->t0, c->t1);
-    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-    (void)hipFree(dd);
-    if (du) (void)hipFree(du);
-    HIP_TRY(err);
-    return ekf_upload_state(c, e, nullptr, y, saved, pose);
-}
-
-extern "C" int ekf_storage_exponent(const ekf_ctx* c, int e)
-{
-    if (!c) return 0;
-    if (e < 0 || e >= c->cfg.instances) return 0;
-    return c->pexp_h[e];
-}
-
-extern "C" int ekf_rescale(ekf_ctx* c, int e, int ex)
-{
-    if (!c) return EKF_EINVAL;
-    if (e < 0 || e >= c->cfg.instances) return EKF_ERANGE;
-    if (c->cfg.precision != EKF_PREC_F16) return EKF_OK;
-    if (ex != EKF_EXP_AUTO && (ex < -24 || ex > 24)) return EKF_ERANGE;
-    int rc = begin_state_write(c);
-    if (rc) return rc;
-    const Dims& d = c->d;
-    int cb = 0;
-    rc = strip_copy(c, e, &cb);
-    if (rc) return rc;
-    void* X = xinst_ptr(c, cur_buf(c), e);
-    double* Rs = strip_of(c, cb, e);
-    double* tmp = nullptr;
-    HIP_TRY(dense_scratch(c, &tmp));
-    std::vector<double> dg(d.n);
-    hipError_t err = ekf::launch_unpack(d, c->cfg.precision, tmp, X, Rs, c->pexp_h[e], c->stream);
-    if (err == hipSuccess)   // the diagonal of the dense copy (stride n + 1)
-        err = hipMemcpy2DAsync(dg.data(), sizeof(double), tmp, sizeof(double) * (d.n + 1), sizeof(double),
-                               d.n, hipMemcpyDeviceToHost, c->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-    if (err == hipSuccess) {
-        double vmax = 0.0;
-        for (int i = 3; i < d.n; i++) vmax = std::max(vmax, std::fabs(dg[i]));
-        rc = set_exponent(c, e, ex == EKF_EXP_AUTO ? choose_exponent(c, vmax) : ex);
-        if (rc == EKF_OK) rc = set_plane_scale(c, e, vmax);
-        if (rc == EKF_OK) {
-            err = ekf::launch_pack(d, c->cfg.precision, tmp, X, Rs, c->tile_rc, c->pexp_h[e], c->stream);
-            if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-        }
-    }
-    HIP_TRY(err);
-    return rc;
-}
-
-extern "C" int ekf_get_pose_cov(ekf_ctx* c, int e, double P33[9])
-{
-    if (!c || !P33) return EKF_EINVAL;
-    if (e < 0 || e >= c->cfg.instances) return EKF_ERANGE;
-    if (c->mirror_epoch != 0 && c->mirror_epoch == c->scan_epoch) {
-        // the robot block the last synchronous call's scan committed (no launch since)
-        memcpy(P33, c->h_r33 + 9 * (size_t)e, sizeof(double) * 9);
-        return EKF_OK;
-    }
-    const Dims& d = c->d;
-    int cb = 0;
-    const int rc = strip_copy(c, e, &cb);
-    if (rc) return rc;
-    for (int a = 0; a < 3; a++)
-        HIP_TRY(hipMemcpyAsync(P33 + 3 * a, strip_of(c, cb, e) + (size_t)a * d.n,
-                               sizeof(double) * 3, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return EKF_OK;
-}
-
-// ---- Robot::getEllipse (Robot.cpp:73-124) on the 2×2 pose block -------------------------
-// The reference calls gsl_eigen_nonsymmv on [[P00, P01], [P10, P11]] (GSL is not vendored and its
-// version is unpinned, CMakeLists.txt:43-51), sorts with GSL_EIGEN_SORT_ABS_ASC and publishes
-// atan2(Re v0, Re v1) of the eigenvector of the larger |λ|. Restated from GSL's published
-// algorithm (gsl/eigen/nonsymmv.c with its defaults: no balancing; gsl/eigen/francis.c):
-//   * a 2×2 matrix is already Hessenberg (Z = I); the Francis QR of a 2×2 block is the
-//     standardisation francis_schur_standardize (LAPACK dlanv2): [a b; c d] = Z [a' b'; 0 d'] Zᵀ
-//     with Z = [[cs, -sn], [sn, cs]] (gsl_blas_drot applied to the columns of I);
-//   * right eigenvectors of the Schur form by back substitution, x = (1, 0) for a' and
-//     x = (-b'/(a'-d'), 1) for d' (denominator floored at smin), back-transformed v = Z·x and
-//     scaled to unit 2-norm (gslcblas dnrm2) — positive scalings only, so the sign is Z's;
-//   * eigenvalues in diagonal order (a', d'), then sorted by |λ| ascending (selection sort,
-//     ties keep their order).
-// A complex pair (c' != 0: not produced by a symmetric covariance block) returns 0.
-namespace {
-inline double gsl_sign(double x) { return x >= 0.0 ? 1.0 : -1.0; }
-
-inline double gsl_hypot_(double x, double y)
-{
-    const double xa = fabs(x), ya = fabs(y);
-    const double mn = xa < ya ? xa : ya, mx = xa < ya ? ya : xa;
-    if (mn == 0.0) return mx;
-    const double u = mn / mx;
-    return mx * sqrt(1.0 + u * u);
-}
-
-inline double cblas_dnrm2_2(double x0, double x1)
-{
-    double scale = 0.0, ssq = 1.0;
-    const double xs[2] = {x0, x1};
-    for (int i = 0; i < 2; i++) {
-        if (xs[i] != 0.0) {
-            const double ax = fabs(xs[i]);
-            if (scale < ax) {
-                ssq = 1.0 + ssq * (scale / ax) * (scale / ax);
-                scale = ax;
-            } else {
-                ssq += (ax / scale) * (ax / scale);
-            }
-        }
-    }
-    return scale * sqrt(ssq);
-}
-
-int gsl_ellipse_2x2(const double P[4], float axii[2], float* angle)
-{
-    for (int k = 0; k < 4; k++)
-        if (!isfinite(P[k])) return 0;
-    double a = P[0], b = P[1], c = P[2], d = P[3];
-    double cs, sn;
-    const double eps = 2.220446049250313e-16;   // GSL_DBL_EPSILON
-    if (c == 0.0) {
-        cs = 1.0;
-        sn = 0.0;
-    } else if (b == 0.0) {
-        cs = 0.0;
-        sn = 1.0;
-        const double t = d;
-        d = a;
-        a = t;
-        b = -c;
-        c = 0.0;
-    } else if ((a - d) == 0.0 && gsl_sign(b) != gsl_sign(c)) {
-        cs = 1.0;
-        sn = 0.0;
-    } else {
-        const double tmp = a - d;
-        double p = 0.5 * tmp;
-        const double bcmax = fmax(fabs(b), fabs(c));
-        const double bcmis = fmin(fabs(b), fabs(c)) * gsl_sign(b) * gsl_sign(c);
-        const double scale = fmax(fabs(p), bcmax);
-        double z = (p / scale) * p + (bcmax / scale) * bcmis;
-        if (z >= 4.0 * eps) {
-            z = p + gsl_sign(p) * fabs(sqrt(scale) * sqrt(z));
-            a = d + z;
-            d -= (bcmax / z) * bcmis;
-            const double tau = gsl_hypot_(c, z);
-            cs = z / tau;
-            sn = c / tau;
-            b -= c;
-            c = 0.0;
-        } else {
-            const double sigma = b + c;
-            const double tau = gsl_hypot_(sigma, tmp);
-            cs = sqrt(0.5 * (1.0 + fabs(sigma) / tau));
-            sn = -(p / (tau * cs)) * gsl_sign(sigma);
-            const double aa = a * cs + b * sn, bb = -a * sn + b * cs;
-            const double cc = c * cs + d * sn, dd = -c * sn + d * cs;
-            a = aa * cs + cc * sn;
-            b = bb * cs + dd * sn;
-            c = -aa * sn + cc * cs;
-            d = -bb * sn + dd * cs;
-            const double t2 = 0.5 * (a + d);
-            a = d = t2;
-            if (c != 0.0) {
-                if (b != 0.0) {
-                    if (gsl_sign(b) == gsl_sign(c)) {
-                        const double sab = sqrt(fabs(b)), sac = sqrt(fabs(c));
-                        p = gsl_sign(c) * fabs(sab * sac);
-                        const double tau2 = 1.0 / sqrt(fabs(b + c));
-                        a = t2 + p;
-                        d = t2 - p;
-                        b -= c;
-                        c = 0.0;
-                        const double cs1 = sab * tau2, sn1 = sac * tau2;
-                        const double t3 = cs * cs1 - sn * sn1;
-                        sn = cs * sn1 + sn * cs1;
-                        cs = t3;
-                    }
-                } else {
-                    b = -c;
-                    c = 0.0;
-                    const double t3 = cs;
-                    cs = -sn;
-                    sn = t3;
-                }
-            }
-        }
-    }
-    if (c != 0.0) return 0;   // complex pair
-    // eigenvectors: Z = [[cs, -sn], [sn, cs]]
-    double v[2][2];
-    v[0][0] = cs;
-    v[0][1] = sn;
-    {
-        const double smlnum = 2.2250738585072014e-308 * (2.0 / eps);
-        const double smin = fmax(eps * fabs(d), smlnum);
-        double den = a - d;
-        if (fabs(den) < smin) den = smin;
-        const double x0 = -b / den;
-        v[1][0] = x0 * cs + (-sn);
-        v[1][1] = x0 * sn + cs;
-    }
-    for (int k = 0; k < 2; k++) {
-        // back substitution ends with a max-norm scaling (as LAPACK dtrevc), the workspace
-        // normalises to unit 2-norm afterwards (nonsymmv_normalize_eigenvectors)
-        const double emax = fmax(fabs(v[k][0]), fabs(v[k][1]));
-        if (emax > 0.0) {
-            const double remax = 1.0 / emax;
-            v[k][0] *= remax;
-            v[k][1] *= remax;
-        }
-        const double nr = cblas_dnrm2_2(v[k][0], v[k][1]);
-        if (nr > 0.0) {
-            const double sc = 1.0 / nr;
-            v[k][0] *= sc;
-            v[k][1] *= sc;
-        }
-    }
-    double lam[2] = {a, d};
-    int ord[2] = {0, 1};
-    if (fabs(lam[1]) < fabs(lam[0])) {
-        ord[0] = 1;
-        ord[1] = 0;
-    }
-    for (int i = 0; i < 2; i++) axii[i] = 2.f * (float)sqrt(5.991 * fabs(lam[ord[i]]));
-    *angle = (float)atan2(v[ord[1]][0], v[ord[1]][1]);
-    return 1;
-}
-}  // namespace
-
-extern "C" int ekf_ellipse_of_block(const double P22[4], float axii[2], float* angle)
-{
-    if (!P22 || !axii || !angle) return -EKF_EINVAL;
-    return gsl_ellipse_2x2(P22, axii, angle);
-}
-
-extern "C" int ekf_get_ellipse(ekf_ctx* c, int e, float axii[2], float* angle)
-{
-    // Robot::getEllipse (Robot.cpp:73-124) on P_t0[0:2, 0:2] of instance e (see above)
-    if (!c || !axii || !angle) return -EKF_EINVAL;
-    double P33[9];
-    int rc = ekf_get_pose_cov(c, e, P33);
-    if (rc) return -rc;
-    const double P22[4] = {P33[0], P33[1], P33[3], P33[4]};
-    return gsl_ellipse_2x2(P22, axii, angle);
-}
-
-extern "C" size_t ekf_landmark_block_bytes(const ekf_ctx* c)
-{
-    return c ? c->xinst * c->elem : 0;
-}
-
-extern "C" int ekf_state_dim(const ekf_ctx* c) { return c ? c->d.n : 0; }
-
-// ---------------------------------------------------------------------------------------
-// One instance with its landmark block partitioned over ranks: this
-// context (ekf_shard_create) stores the packed tiles of its tile rows only; the scan runs as
-// phases of ekf::shard_kernel over every landmark (replicated state), and the caller sums the
-// [N][4] exchange buffer over the ranks between phases: the diagonal blocks after begin, the
-// winner's column after each line. Everything is stream-ordered on the context stream: no host
-// round trip until ekf_shard_end.
-
-static ekf::ShardParams shard_params(ekf_ctx* c, int phase, double* buf, double* cols = nullptr)
-{
-    ekf::ShardParams p;
-    memset(&p, 0, sizeof(p));
-    p.d = c->d;
-    p.phase = phase;
-    p.line = c->sh_line;
-    p.L = c->sh_L;
-    p.r_mode = c->cfg.r_mode;
-    p.gate = c->cfg.mahalanobis;
-    p.enc_noise = c->cfg.encoder_noise;
-    const int np = (int)(c->nsteps - c->pend0);
-    p.npend = np;
-    p.Pread = xview(c, c->base);
-    p.t0 = c->t0;
-    p.t1 = c->t1;
-    for (int q = 0; q < np; q++) p.pend[q] = slot_of(c, c->pend0 + q);
-    p.cur = slot_of(c, c->nsteps);
-    p.Rs = strip_of(c, 0, 0);
-    p.y = mean_of(c, 0, 0);
-    p.pose = c->pose;
-    p.saved = c->saved;
-    p.rob = c->sh_rob;
-    p.rec = c->sh_rec;
-    p.hist = c->sh_hist;
-    p.flags = c->sh_flags;
-    p.pkg = c->sh_pkg;
-    p.ctl = c->sh_ctl;
-    p.col = buf;
-    p.cols = cols;
-    p.enc = c->d_enc;
-    p.lines = c->d_lines;
-    p.pexp = c->pexp;
-    p.reset_margin = c->cfg.reset_margin;
-    return p;
-}
-
-// a HIP failure inside a scan abandons it (slam_ekf.h ekf_shard_abort)
-#define SH_TRY(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) {                                                             \
-            fprintf(stderr, "slam_ekf: %s failed: %s\n", #expr, hipGetErrorString(_e));     \
-            c->sh_open = 0;                                                                 \
-            return EKF_EDEVICE;                                                             \
-        }                                                                                   \
-    } while (0)
-
-extern "C" int ekf_shard_tiles(const ekf_ctx* c, int* row_begin, int* row_end)
-{
-    if (!c || c->sh_world <= 0 || !row_begin || !row_end) return EKF_EINVAL;
-    *row_begin = c->sh_r0;
-    *row_end = c->sh_r1;
-    return EKF_OK;
-}
-
-extern "C" size_t ekf_shard_buffer_words(const ekf_ctx* c) { return (c && c->sh_world > 0) ? 4 * (size_t)c->d.N : 0; }
-
-extern "C" int ekf_shard_begin(ekf_ctx* c, const double enc[3], const ekf_line* lines, int nlines, double* buf)
-{
-    if (!c || c->sh_world <= 0 || !enc || !buf || (nlines > 0 && !lines) || c->sh_open) return EKF_EINVAL;
-    if (nlines < 0 || nlines > c->d.max_lines) return EKF_ERANGE;
-    c->sh_line = 0;
-    c->sh_L = nlines;
-    c->sh_open = 1;
-    c->sh_diag = 0;
-    // the inputs travel as kernel arguments of the first phase, which stores them for the later
-    // ones (stream-ordered: no host staging copy, no wait for the previous scan)
-    ekf::ShardParams p = shard_params(c, ekf::SH_BEGIN, buf);
-    for (int k = 0; k < 3; k++) p.enc_v[k] = enc[k];
-    for (int i = 0; i < c->d.max_lines; i++) {
-        if (i < nlines) p.lines_v[i] = lines[i];
-        else memset(&p.lines_v[i], 0, sizeof(ekf_line));
-    }
-    SH_TRY(ekf::launch_shard(p, c->cfg.precision, c->stream));
-    return EKF_OK;
-}
-
-extern "C" int ekf_shard_line(ekf_ctx* c, int line, double* buf)
-{
-    if (!c || c->sh_open != 1 || !buf || line != c->sh_line) return EKF_EINVAL;
-    if (line < 0 || line >= c->sh_L) return EKF_ERANGE;
-    if (!c->sh_diag) {   // the summed diagonal blocks of begin's exchange
-        SH_TRY(ekf::launch_shard(shard_params(c, ekf::SH_DIAG, buf), c->cfg.precision, c->stream));
-        c->sh_diag = 1;
-    }
-    SH_TRY(ekf::launch_shard(shard_params(c, ekf::SH_GATE, buf), c->cfg.precision, c->stream));
-    SH_TRY(ekf::launch_shard(shard_params(c, ekf::SH_COLUMN, buf), c->cfg.precision, c->stream));
-    return EKF_OK;
-}
-
-extern "C" int ekf_shard_apply(ekf_ctx* c, int line, const double* buf)
-{
-    if (!c || c->sh_open != 1 || !buf || line != c->sh_line) return EKF_EINVAL;
-    double* b = const_cast<double*>(buf);   // (read only by these phases)
-    SH_TRY(ekf::launch_shard(shard_params(c, ekf::SH_APPLY, b), c->cfg.precision, c->stream));
-    SH_TRY(ekf::launch_shard(shard_params(c, ekf::SH_ROBOT, b), c->cfg.precision, c->stream));
-    c->sh_line++;
-    return EKF_OK;
-}
-
-extern "C" size_t ekf_shard_spec_buffer_words(const ekf_ctx* c)
-{
-    return (c && c->sh_world > 0) ? 4 * (size_t)c->d.N * (size_t)c->d.max_lines : 0;
-}
-
-extern "C" int ekf_shard_speculate(ekf_ctx* c, const double* buf, double* cols)
-{
-    if (!c || c->sh_open != 1 || !buf || !cols || c->sh_line != 0 || c->sh_L == 0) return EKF_EINVAL;
-    double* b = const_cast<double*>(buf);   // (read only by SH_DIAG)
-    ekf::ShardParams pg = shard_params(c, ekf::SH_GUESS, b);
-    pg.diag_first = !c->sh_diag;   // (SH_DIAG fused into the guesses' launch)
-    c->sh_diag = 1;
-    SH_TRY(ekf::launch_shard(pg, c->cfg.precision, c->stream));
-    if (c->spec == 2)   // test hook (EKF_OPT_SPECULATE = 2): every line guesses landmark 0
-        SH_TRY(hipMemsetAsync(c->sh_ctl + ekf::SC_GUESS, 0, sizeof(int) * c->d.max_lines, c->stream));
-    SH_TRY(ekf::launch_shard(shard_params(c, ekf::SH_SPEC_COLS, b, cols), c->cfg.precision, c->stream));
-    return EKF_OK;
-}
-
-extern "C" int ekf_shard_run(ekf_ctx* c, const double* cols, double* next_line)
-{
-    if (!c || c->sh_open != 1 || !cols || !next_line || !c->sh_diag || c->sh_line != 0 || c->sh_L == 0)
-        return EKF_EINVAL;
-    ekf::ShardParams p = shard_params(c, ekf::SH_GATE, nullptr, const_cast<double*>(cols));
-    p.next_out = next_line;
-    // the run's workgroups exchange through the association kernel's mailbox (unused by a
-    // partitioned context: ⌈N/64⌉ ≥ shard_run_workgroups(N) slots per parity)
-    p.mbox = c->mbox;
-    p.mbw = c->mbw;
-    p.epoch = ++c->scan_epoch;
-    p.spin_log2 = c->spin_log2;
-    SH_TRY(ekf::launch_shard_run(p, c->cfg.precision, c->stream));
-    c->sh_line = -1;   // until ekf_shard_resume
-    return EKF_OK;
-}
-
-extern "C" int ekf_shard_resume(ekf_ctx* c, int line)
-{
-    if (!c || c->sh_open != 1 || c->sh_line != -1 || line < 0 || line > c->sh_L) return EKF_EINVAL;
-    c->sh_line = line;
-    return EKF_OK;
-}
-
-// SH_END with its results mirrored into the pinned host buffers (one instance), so the result
-// needs no copy: only the wait for this kernel, not for a flush behind it. gate (ekf_shard_localize):
-// the ranks' agreement [failure flag, stopping line] on the device; the phase commits only if it
-// says every line ran, and mirrors the pair into h_agree either way
-static int shard_end_launch(ekf_ctx* c, const double* gate)
-{
-    ekf::ShardParams p = shard_params(c, ekf::SH_END, nullptr);
-    int* rh = nullptr;
-    double* ph = nullptr;
-    HIP_TRY(hipHostGetDevicePointer((void**)&rh, c->h_res, 0));
-    HIP_TRY(hipHostGetDevicePointer((void**)&ph, c->h_pose, 0));
-    p.res_host = rh;
-    p.pose_host = ph;
-    if (gate) {
-        double* ah = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void**)&ah, c->h_agree, 0));
-        p.end_gate = gate;
-        p.end_gate_host = ah;
-    }
-    SH_TRY(ekf::launch_shard(p, c->cfg.precision, c->stream));
-    HIP_TRY(hipEventRecord(c->ev_scan, c->stream));
-    return EKF_OK;
-}
-
-// after a committed SH_END: the step joins the deferred flush of the rank's tiles; the results
-// from the mirror once the phase has finished (flushed: the wait was before the flush's launch)
-static int shard_end_finish(ekf_ctx* c, ekf_result* out, bool waited)
-{
-    c->sh_open = 0;
-    c->nsteps++;
-    if (c->nsteps - c->unflushed0 >= c->T) {
-        const int rc = enqueue_flush(c);
-        if (rc) return rc;
-    }
-    if (!waited) HIP_TRY(hipEventSynchronize(c->ev_scan));
-    fill_results(c, out);
-    return EKF_OK;
-}
-
-extern "C" int ekf_shard_end(ekf_ctx* c, ekf_result* out)
-{
-    if (!c || c->sh_open != 1 || c->sh_line != c->sh_L) return EKF_EINVAL;
-    // (with no line, begin's exchange is not consumed: the end needs no diagonal block)
-    const int rc = shard_end_launch(c, nullptr);
-    if (rc) return rc;
-    return shard_end_finish(c, out, false);
-}
-
-extern "C" int ekf_shard_abort(ekf_ctx* c)
-{
-    // before ekf_shard_end nothing of the committed state is written (the phases use the scan's
-    // scratch and the current ring slot, which only ekf_shard_end adds to the schedule)
-    if (!c || c->sh_world <= 0) return EKF_EINVAL;
-    c->sh_open = 0;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return EKF_OK;
-}
-
-// The partitioned instance's scan as one call (ekf_shard_localize): the protocol above with the
-// exchanges on the library's own RCCL communicator (ekf_shard_attach_rccl), so a C++ host (the
-// drop-in Robot over ranks) needs no collective library of its own and a scan costs one call, two
-// host reads (the agreement pair, then the results) and no host staging. RCCL is loaded on first
-// use (dlopen): the library itself does not depend on it.
-namespace {
-struct RcclApi {
-    ncclResult_t (*get_unique_id)(ncclUniqueId*);
-    ncclResult_t (*comm_init_rank)(ncclComm_t*, int, ncclUniqueId, int);
-    ncclResult_t (*all_reduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t);
-    ncclResult_t (*comm_destroy)(ncclComm_t);
-    const char* (*error_string)(ncclResult_t);
-};
-const RcclApi* rccl_api()
-{
-    static RcclApi api;
-    static int state = 0;   // 0 not tried, 1 loaded, -1 unavailable (one thread: the context's)
-    if (state == 0) {
-        state = -1;
-        void* h = nullptr;
-        for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"})
-            if ((h = dlopen(name, RTLD_NOW | RTLD_LOCAL)) != nullptr) break;
-        if (h) {
-            api.get_unique_id = (decltype(api.get_unique_id))dlsym(h, "ncclGetUniqueId");
-            api.comm_init_rank = (decltype(api.comm_init_rank))dlsym(h, "ncclCommInitRank");
-            api.all_reduce = (decltype(api.all_reduce))dlsym(h, "ncclAllReduce");
-            api.comm_destroy = (decltype(api.comm_destroy))dlsym(h, "ncclCommDestroy");
-            api.error_string = (decltype(api.error_string))dlsym(h, "ncclGetErrorString");
-            if (api.get_unique_id && api.comm_init_rank && api.all_reduce && api.comm_destroy && api.error_string)
-                state = 1;
-        }
-        if (state != 1) fprintf(stderr, "slam_ekf: RCCL (librccl.so) not available\n");
-    }
-    return state == 1 ? &api : nullptr;
-}
-}  // namespace
-
-static void rccl_destroy(ekf_ctx* c)
-{
-    const RcclApi* r = c->rccl_comm ? rccl_api() : nullptr;
-    if (r) (void)r->comm_destroy((ncclComm_t)c->rccl_comm);
-    c->rccl_comm = nullptr;
-}
-
-extern "C" int ekf_rccl_unique_id(unsigned char out[128])
-{
-    const RcclApi* r = rccl_api();
-    if (!out) return EKF_EINVAL;
-    if (!r) return EKF_EDEVICE;
-    ncclUniqueId id;
-    if (r->get_unique_id(&id) != ncclSuccess) return EKF_EDEVICE;
-    static_assert(sizeof(id) == 128, "ncclUniqueId");
-    memcpy(out, &id, sizeof(id));
-    return EKF_OK;
-}
-
-extern "C" int ekf_shard_attach_rccl(ekf_ctx* c, const unsigned char id[128], int rank, int world)
-{
-    if (!c || c->sh_world <= 0 || !id || rank != c->sh_rank || world != c->sh_world || c->sh_open) return EKF_EINVAL;
-    const RcclApi* r = rccl_api();
-    if (!r) return EKF_EDEVICE;
-    HIP_TRY(hipSetDevice(c->device));
-    rccl_destroy(c);
-    ncclUniqueId uid;
-    memcpy(&uid, id, sizeof(uid));
-    ncclComm_t comm;
-    const ncclResult_t e = r->comm_init_rank(&comm, world, uid, rank);
-    if (e != ncclSuccess) {
-        fprintf(stderr, "slam_ekf: ncclCommInitRank: %s\n", r->error_string(e));
-        return EKF_EDEVICE;
-    }
-    c->rccl_comm = comm;
-    const size_t words = 4 * (size_t)c->d.N, swords = words * (size_t)c->d.max_lines;
-    if (!c->sh_xbuf || !c->sh_xcols || !c->h_agree) {
-        // all three or none: a failure part way frees what was allocated, so a later attach
-        // allocates again instead of finding one pointer set and the others null
-        auto drop = [c]() {
-            if (c->sh_xbuf) (void)hipFree(c->sh_xbuf);
-            if (c->sh_xcols) (void)hipFree(c->sh_xcols);
-            if (c->h_agree) (void)hipHostFree(c->h_agree);
-            c->sh_xbuf = c->sh_xcols = c->h_agree = nullptr;
-        };
-        drop();
-        if (hipMalloc((void**)&c->sh_xbuf, sizeof(double) * (words + 1)) != hipSuccess ||
-            hipMalloc((void**)&c->sh_xcols, sizeof(double) * (swords + 2)) != hipSuccess ||
-            hipHostMalloc((void**)&c->h_agree, sizeof(double) * 4) != hipSuccess ||
-            hipMemset(c->sh_xbuf, 0, sizeof(double) * (words + 1)) != hipSuccess ||
-            hipMemset(c->sh_xcols, 0, sizeof(double) * (swords + 2)) != hipSuccess) {
-            drop();
-            rccl_destroy(c);
-            return EKF_EDEVICE;
-        }
-    }
-    c->sh_dirty = 0;
-    return EKF_OK;
-}
-
-extern "C" int ekf_shard_localize(ekf_ctx* c, const double enc[3], const ekf_line* lines, int nlines, ekf_result* out)
-{
-    if (!c || c->sh_world <= 0 || !c->rccl_comm || !enc || (nlines > 0 && !lines) || c->sh_open) return EKF_EINVAL;
-    if (nlines < 0 || nlines > c->d.max_lines) return EKF_ERANGE;
-    const RcclApi* r = rccl_api();
-    const int L = nlines;
-    const size_t words = 4 * (size_t)c->d.N, swords = words * (size_t)c->d.max_lines;
-    double* buf = c->sh_xbuf;
-    double* cols = c->sh_xcols;
-    double* agree = cols + swords;   // [failure flag (the columns' flag word), stopping line]
-    ncclComm_t comm = (ncclComm_t)c->rccl_comm;
-    auto sum = [&](double* b, size_t n, ncclRedOp_t op) {
-        return r->all_reduce(b, b, n, ncclFloat64, op, comm, c->stream) == ncclSuccess;
-    };
-    // a phase that fails on one rank must not leave the others waiting in an exchange: every rank
-    // runs the whole exchange sequence, a failed one without further phases, and the summed flag
-    // words tell every rank alike whether to abandon the scan
-    static const double one_l[2] = {1.0, 0.0};
-    auto flag = [&](double* w) {
-        c->sh_dirty = 1;
-        return hipMemcpyAsync(w, one_l, sizeof(double), hipMemcpyHostToDevice, c->stream) == hipSuccess;
-    };
-    if (c->sh_dirty) {
-        HIP_TRY(hipMemsetAsync(buf + words, 0, sizeof(double), c->stream));
-        HIP_TRY(hipMemsetAsync(agree, 0, 2 * sizeof(double), c->stream));
-        c->sh_dirty = 0;
-    }
-    int err = ekf_shard_begin(c, enc, lines, L, buf);
-    if (err && !flag(buf + words)) return EKF_EDEVICE;
-    if (!sum(buf, words + 1, ncclSum)) return EKF_EDEVICE;
-    int first = 0;
-    bool abandon = false, spec_all = false;
-    if (c->spec && L > 0) {
-        if (!err) err = ekf_shard_speculate(c, buf, cols);
-        if (err && !flag(agree)) return EKF_EDEVICE;
-        if (!sum(cols, swords + 1, ncclSum)) return EKF_EDEVICE;
-        if (!err) err = ekf_shard_run(c, cols, agree + 1);
-        if (err) {
-            const double v[2] = {1.0, (double)L};
-            HIP_TRY(hipMemcpyAsync(agree, v, sizeof(v), hipMemcpyHostToDevice, c->stream));
-            c->sh_dirty = 1;
-        }
-        if (!sum(agree, 2, ncclMax)) return EKF_EDEVICE;
-        // the end phase goes behind the run before the host reads the agreement: it commits only if
-        // every line ran on every rank (the common case: one host round trip per scan), and leaves
-        // everything untouched otherwise, when the lines from the agreed one follow as below
-        bool gated = false;
-        if (!err) {
-            c->sh_line = L;
-            err = shard_end_launch(c, agree);
-            gated = !err;
-        }
-        if (!gated)
-            HIP_TRY(hipMemcpyAsync(c->h_agree, agree, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        abandon = c->h_agree[0] > 0.0 || c->h_agree[1] > (double)L;   // (past L: a run timed out)
-        first = abandon ? L : (int)c->h_agree[1];
-        if (gated && !abandon && first == L) return shard_end_finish(c, out, true);
-        if (gated) c->sh_line = -1;   // (not committed: the run's state stands, as after ekf_shard_run)
-        // (host bookkeeping only, on the agreed line: it fails on every rank alike or on none)
-        if (!abandon && !err) err = ekf_shard_resume(c, first);
-        spec_all = first == L;
-    }
-    for (int i = first; i < L; i++) {
-        if (!err) err = ekf_shard_line(c, i, buf);
-        if (err && !flag(buf + words)) return EKF_EDEVICE;
-        if (!sum(buf, words + 1, ncclSum)) return EKF_EDEVICE;
-        if (!err) err = ekf_shard_apply(c, i, buf);
-    }
-    double failed;
-    if (spec_all) {
-        failed = c->h_agree[0];   // (the agreement carried every failure flag)
-    } else {
-        if (L > first) {
-            // the last line's apply ran after its exchange: one more word, the MAX over the ranks
-            // of the summed flags and of every rank's failure since, so that a rank whose apply
-            // failed does not abandon the scan alone while its peers commit it
-            if (err && !flag(buf + words)) return EKF_EDEVICE;
-            if (!sum(buf + words, 1, ncclMax)) return EKF_EDEVICE;
-        }
-        HIP_TRY(hipMemcpyAsync(c->h_agree + 2, buf + words, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        failed = c->h_agree[2];
-    }
-    if (abandon || failed > 0.0 || err) {
-        c->sh_dirty = 1;
-        (void)ekf_shard_abort(c);
-        return err ? err : EKF_EDEVICE;   // (a peer's phase failed, or the run's exchange timed out)
-    }
-    return ekf_shard_end(c, out);
 }
 
 extern "C" int ekf_profile_enable(ekf_ctx* c, int enable)

@@ -1,7 +1,10 @@
-// ekf_ctx.h — the context behind the C-ABI and what its host units share (internal): ekf_api.hip (the
-// core: creation, the schedule, scans, flushes, state upload / download, the partitioned instance),
-// ekf_read.hip (the calls that read without draining: covariance queries, gate, joint gate, joint search) and
-// ekf_copy.hip (the calls that copy instances without draining: ekf_resample, the instance images).
+// ekf_ctx.h — the context behind the C-ABI and everything its five host units share (internal):
+//   ekf_api.hip    the core: creation, options, the schedule (scans, flushes, drain), results, profiling;
+//   ekf_state.hip  the calls that read or write one instance's state without a scan: reset, upload,
+//                  download, low-rank initialisation, rescale, pose covariance, ellipse (ekf_ellipse.h);
+//   ekf_shard.hip  the partitioned instance: the ekf_shard_* protocol, RCCL, ekf_shard_localize;
+//   ekf_read.hip   the calls that read without draining: covariance queries, gate, joint gate, joint search;
+//   ekf_copy.hip   the calls that copy instances without draining: ekf_resample, the instance images.
 #pragma once
 
 #include <stdio.h>
@@ -113,6 +116,7 @@ struct ekf_ctx {
     double* sh_xbuf;          // ... and ekf_shard_localize's exchange buffers (device): [N][4] + flag,
     double* sh_xcols;         // [L][N][4] + flag + stopping line
     double* h_agree;          // pinned: the agreement pair and a flag word
+    double* hd_agree;         // (its device pointer)
     int sh_dirty;             // a failed scan left nonzero flag words
     int* h_res;
     double* h_pose;
@@ -188,7 +192,27 @@ struct ekf_ctx {
         }                                                                                   \
     } while (0)
 
-// ---- the core's helpers the other host units use (ekf_api.hip); not exported from the library ----
+static inline int cur_buf(const ekf_ctx* c) { return c->last_out; }
+
+// instance e's stored tiles in buffer buf (xview: the kernels' view of instance 0)
+static inline char* xinst_ptr(const ekf_ctx* c, int buf, int e)
+{
+    return (char*)c->X[buf] + (size_t)e * c->xinst * c->elem;
+}
+
+// copy cb (strip_copy) of instance e's robot strip and mean
+static inline double* strip_of(const ekf_ctx* c, int cb, int e)
+{
+    return c->Rs + ((size_t)cb * c->cfg.instances + e) * 3 * c->d.n;
+}
+
+static inline double* mean_of(const ekf_ctx* c, int cb, int e)
+{
+    return c->y + ((size_t)cb * c->cfg.instances + e) * c->d.n;
+}
+
+// ---- what crosses the host units; not exported from the library. Defined in ekf_api.hip, except the
+// last two ----
 #pragma GCC visibility push(hidden)
 bool dev_alloc(ekf_ctx* c, void** p, size_t bytes);   // zeroed device memory on the context's list
 int pinned_reserve(PinnedBuf& b, size_t bytes);       // EKF_OK, EKF_ENOMEM or EKF_EDEVICE (b then empty)
@@ -198,4 +222,10 @@ void* xview(const ekf_ctx* c, int buf);
 // Behind work enqueued on S that reads or writes X[base] or the ring outside a scan: the next flush on D
 // waits for it too
 int end_read(ekf_ctx* c);
+int drain(ekf_ctx* c);           // flushes the partial group, waits for S and D: X[last_out] is the block
+int enqueue_flush(ekf_ctx* c);   // one flush of the steps [unflushed0, nsteps), if any (who adds a step calls it at T)
+void fill_results(const ekf_ctx* c, ekf_result* out);   // out[E] (or null) from the host copies h_res, h_pose
+int strip_copy(ekf_ctx* c, int e, int* cb);   // waits for S; *cb: instance e's committed strip and mean, 0 or 1
+int set_robot_ctor(ekf_ctx* c, int e, double x, double y, double th);   // (ekf_state.hip) Robot::Robot; waits for S
+void rccl_destroy(ekf_ctx* c);   // (ekf_shard.hip) the context's communicator, if it has one
 #pragma GCC visibility pop

@@ -55,7 +55,7 @@ namespace ekf {
 // flush and in the on-read replay alike, so the stored value never depends on when it is flushed.
 // It holds 2^x·P with a per-instance exponent x (ScanParams/DowndateParams::pexp, default 10:
 // |P| < 64 representable, normal down to 6e-8; chosen at upload from the largest landmark
-// variance, ekf_api.hip choose_exponent). The fp16 path computes in that scaled domain
+// variance, ekf_state.hip choose_exponent). The fp16 path computes in that scaled domain
 // throughout: the scan writes the U operand scaled by 2^x (exact), so flush and on-read replay
 // both run acc = 2^x·X − (2^x·U)·Vᵀ, bit-for-bit 2^x × the unscaled chain, and round with two
 // conversions per element; values leave the scaled domain only where they are read as P.

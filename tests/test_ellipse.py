@@ -1,6 +1,6 @@
 """Robot::getEllipse (slam_ros/Robot.cpp:73-124) in GSL's convention, CPU only.
 
-The library's host restatement (ekf_ellipse_of_block, slam_ros_amd/csrc/ekf_api.hip) and the
+The library's host restatement (ekf_ellipse_of_block, slam_ros_amd/csrc/ekf_ellipse.h) and the
 oracle's independent Python restatement (oracle/oracle.py gsl_ellipse) of gsl_eigen_nonsymmv +
 GSL_EIGEN_SORT_ABS_ASC must agree bit for bit (float32 outputs), including the eigenvector sign
 that decides the published angle (main.cpp:154-168 publishes it as robotPosition.rotation.z).
