@@ -42,7 +42,8 @@ extern "C" {
  *    ekf_query_marginals, ekf_query_joint_device; ekf_gate_lines, ekf_gate_lines_device;
  *    ekf_gate_joint, ekf_gate_joint_device; ekf_resample, ekf_copy_instance;
  *    ekf_instance_image_bytes, ekf_export_instances(_device), ekf_import_instances(_device);
- *    ekf_associate_joint, ekf_associate_joint_device. */
+ *    ekf_associate_joint, ekf_associate_joint_device; ekf_gate_candidates_device,
+ *    ekf_assoc_weights_device, ekf_resample_plan_device, ekf_resample_device. */
 #define SLAM_EKF_ABI_VERSION 3
 #define EKF_MAX_LINES 64 /* lines per scan per instance; main.cpp:99 reserves 20 */
 
@@ -513,6 +514,75 @@ int ekf_resample(ekf_ctx* ctx, const int32_t* src /* [E], host */);
 /* ekf_resample with src = identity except src[dst] = from (from must keep its state: always true
  * here). EKF_ERANGE for dst or from outside [0, E); dst == from is valid and launches nothing. */
 int ekf_copy_instance(ekf_ctx* ctx, int dst, int from);
+
+/* The ensemble's hypothesis loop without a host stop: the four stages between and behind
+ * ekf_gate_lines_device and ekf_associate_joint_device, so that a scan's gate -> candidates -> joint search
+ * -> weights -> resampling plan -> copy is a sequence of enqueues on the context stream. Device forms only
+ * (the host forms are ekf.gate_candidates, ekf.resample_plan and ekf_resample); every buffer is device
+ * memory, every call asynchronous on the context stream behind the work enqueued so far. None drains,
+ * flushes, adds a step or moves the schedule. The reference has one filter and no such members.
+ * EKF_EINVAL for a partitioned context, as their neighbours.
+ *
+ * ekf_gate_candidates_device: the candidate lists ekf_associate_joint_device takes, from the matrix
+ *   ekf_gate_lines_device wrote. A pure function of that matrix: it reads no filter state.
+ *   Landmark j is a member of line i's list when sqrt(fabs(d2[e][i][j])) <= gate (NaN and +inf fail). The
+ *   list is ordered by that square root, ascending, the lower landmark first on ties; it keeps the first C
+ *   members and is padded with -1. count[e][i], if given, is the number of members before the cut. Rows
+ *   i >= nlines[e] get -1 / 0. The fp64 square root is correctly rounded, so the lists are bit for bit
+ *   those of ekf.gate_candidates on the same matrix. No cap on the members inside the gate, and no
+ *   dependence on scheduling: one workgroup per (line, instance) finds, C times, the smallest (key, j)
+ *   strictly above the previous one.
+ *   Errors: EKF_ERANGE for C outside [1, EKF_ASSOC_MAX_CAND]; EKF_EINVAL for a NULL context, d2, nlines or
+ *   cand, or a gate that is not a finite number >= 0. */
+int ekf_gate_candidates_device(ekf_ctx* ctx, const double* d_d2 /* [E][max_lines][N] */, const int32_t* d_nlines /* [E] */,
+                               int C, double gate, int32_t* d_cand /* [E][max_lines][C] */,
+                               int32_t* d_count /* [E][max_lines] or NULL */);
+/* ekf_assoc_weights_device: the instances' weights from the search's hits. With m, d2, logdet of hits[e],
+ *   lw_e = -(d2 + logdet) / 2 - m log(2 pi) + (nlines[e] - m) log_unassigned + logprior[e]
+ *   (log_unassigned: the caller's term per line left out, 0 for the documented likelihood, not applied
+ *   when no line is left out; logprior NULL: 0) and weights[e] = exp(lw_e - max lw): the best instance has
+ *   weight exactly 1. An instance whose hit carries EKF_AS_INVALID, or whose lw is not finite, is out:
+ *   weight 0, and it does not enter the maximum. EKF_AS_TRUNCATED hits are used as they are (still
+ *   feasible). Every instance out: all weights 0, which ekf_resample_plan_device reports. One launch.
+ *   Errors: EKF_EINVAL for a NULL context, hits, nlines or weights. */
+int ekf_assoc_weights_device(ekf_ctx* ctx, const ekf_assoc_hit* d_hits /* [E] */, const int32_t* d_nlines /* [E] */,
+                             double log_unassigned, const double* d_logprior /* [E] or NULL */,
+                             double* d_weights /* [E] */);
+/* ekf_resample_plan_device: systematic resampling (ekf.resample_plan) as a list ekf_resample_device takes.
+ *   total = sum of the weights and edges = running sum of q_e = w_e / total, both accumulated in ascending
+ *   index order; point k = (u + k) / E goes to min(upper_bound(edges, point), last index with w > 0).
+ *   Every instance with a point keeps its state (src[e] = e); the slots without one, ascending, take the
+ *   surplus copies of the survivors in ascending survivor order: src[src[e]] == src[e] always.
+ *   info (if given): ess = 1 / sum q^2, total, copies = the number of e with src[e] != e, and status:
+ *   EKF_RP_KEPT when !(ess < ess_below) (pass +inf for "always resample"): the identity list;
+ *   EKF_RP_INVALID when a weight is negative or not finite or the total is not a finite positive number:
+ *   the identity list, ess 0.
+ *   Errors: EKF_ERANGE for u outside [0, 1); EKF_EINVAL for a NULL context, weights or src, or a NaN
+ *   ess_below. */
+enum { EKF_RP_INVALID = 1, EKF_RP_KEPT = 2 };   /* ekf_plan_info.status */
+typedef struct ekf_plan_info {
+    int32_t status;   /* EKF_RP_* */
+    int32_t copies;   /* instances the plan overwrites */
+    double ess;       /* effective sample size of the weights */
+    double total;     /* their sum */
+} ekf_plan_info;
+int ekf_resample_plan_device(ekf_ctx* ctx, const double* d_weights /* [E] */, double u, double ess_below,
+                             int32_t* d_src /* [E] */, ekf_plan_info* d_info /* may be NULL */);
+/* ekf_resample_device: ekf_resample with the list in device memory, written by earlier work on the
+ *   stream. The contract is ekf_resample's: everything an instance owns travels, the pending ring slots
+ *   included, nothing drains, and an instance with src[e] == e is bit-identical to the same instance of a
+ *   context that never made the call.
+ *   The list is checked on the device, all or nothing: an entry outside [0, E) (never used as an index) or
+ *   a source that is not a fixed point copies nothing, leaves every byte as it was, and d_status (if
+ *   given) receives EKF_ERANGE or EKF_EINVAL as ekf_resample would return; an accepted list gives EKF_OK.
+ *   The return value covers only what the host can see. The copy is dealt over the overwritten instances
+ *   found on the device; the identity list moves no byte.
+ *   The host's mirror of the storage exponents becomes stale: the next ekf_storage_exponent, state
+ *   transfer or image export re-reads it from the device (one small synchronous copy there, none on the
+ *   per-scan path).
+ *   Errors: EKF_EINVAL for a NULL context or list, a partitioned context, or a call between ekf_predict
+ *   and ekf_update. */
+int ekf_resample_device(ekf_ctx* ctx, const int32_t* d_src /* [E], device */, int32_t* d_status /* device, may be NULL */);
 
 /* Instance images: instances moved between contexts (the ranks of an ensemble sharded over GPUs, a
  * file), where ekf_resample moves them inside one. The reference has one filter and no such member.

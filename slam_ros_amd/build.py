@@ -82,16 +82,16 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-mllvm", "-amdgpu-mfma-vgpr-for
 # unit_*.hip includes the device code its kernels need (the flush units a header per flush family,
 # the query unit ekf_device.h alone, the gate unit ekf_gate.h, the joint and search units
 # ekf_joint_parts.h above it, the resample and image units only their tables' headers and the shared
-# copy body, the others the association kernels, ekf_kernels.hip, which is not compiled on its own)
+# copy body, the loop unit ekf_loop_plan.h alone, the others the association kernels, ekf_kernels.hip, which is not compiled on its own)
 # and defines the launchers that instantiate them; they compile in parallel with the five host units,
 # which define no kernels and share ekf_ctx.h: ekf_api.hip (the context and the schedule), ekf_state.hip
 # (state transfers, ellipse), ekf_shard.hip (the partitioned instance, RCCL), ekf_read.hip (queries, gate,
-# joint gate, joint search) and ekf_copy.hip (resample, images).
+# joint gate, joint search, candidates, weights) and ekf_copy.hip (resample, its plan, images).
 UNITS = ["unit_flush_f16x3.hip", "unit_flush_exact.hip", "unit_scan.hip", "unit_scan_nt128.hip",
          "unit_scan_nt64.hip", "unit_flush_2x4.hip", "unit_flush_bf16x6.hip", "unit_shard_pack.hip",
          "unit_flush_quad.hip", "unit_query.hip", "unit_gate.hip", "unit_joint.hip", "unit_assoc.hip",
          "ekf_api.hip", "ekf_state.hip", "ekf_shard.hip", "ekf_read.hip", "ekf_copy.hip",
-         "unit_resample.hip", "unit_image.hip"]
+         "unit_resample.hip", "unit_image.hip", "unit_resample_device.hip", "unit_loop.hip"]
 
 
 def source_deps(csrc: str = CSRC) -> list[str]:

@@ -177,6 +177,17 @@ int strip_copy(ekf_ctx* c, int e, int* cb)
     return EKF_OK;
 }
 
+// The host copy of the storage exponents after ekf_resample_device, whose list the host never saw
+int pexp_mirror(ekf_ctx* c)
+{
+    if (!c->pexp_stale) return EKF_OK;
+    HIP_TRY(hipMemcpyAsync(c->pexp_h.data(), c->pexp, sizeof(int) * c->pexp_h.size(), hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->pexp_stale = 0;
+    return EKF_OK;
+}
+
 // ---- create_ctx's steps, in the order it takes them. Each returns a status and leaves what it made on
 // the context's lists or in its named members, so one failure path (free_all) serves them all.
 #define ALLOC(ptr, bytes) do { if (!dev_alloc(c, (void**)&(ptr), (bytes))) return EKF_ENOMEM; } while (0)

@@ -1,5 +1,7 @@
 // ekf_copy.hip — the calls that copy instances without draining the flush (slam_ekf.h): ekf_resample and
-// ekf_copy_instance (table: ekf_resample_plan.h; kernel: unit_resample.hip) and the instance images,
+// ekf_copy_instance (table: ekf_resample_plan.h; kernel: unit_resample.hip), ekf_resample_device (the same
+// arrays as pieces; kernels: unit_resample_device.hip) with ekf_resample_plan_device, which writes its
+// list (ekf_loop_plan.h; kernel: unit_loop.hip), and the instance images,
 // ekf_export_instances* / ekf_import_instances* (table: ekf_image_plan.h; kernel of the device forms:
 // unit_image.hip).
 #include <stdint.h>
@@ -69,19 +71,19 @@ static int rs_wait(ekf_ctx* c)
 // One table-driven copy on S. The table goes into the context's pinned buffer, which is rewritten only
 // after the last launch that reads it (rs_ev); launch(table, nseg) enqueues the kernel on the table's
 // device address. The caller closes with end_read: the next flush on D waits for the copy too.
-template <typename F>
-static int run_table(ekf_ctx* c, const std::vector<ekf::CopySeg>& table, F launch)
+template <typename Seg, typename F>
+static int run_table(ekf_ctx* c, const std::vector<Seg>& table, F launch)
 {
     if (c->rs_pending) HIP_TRY(hipEventSynchronize(c->rs_ev));
     c->rs_pending = 0;
     if (!c->rs_ev) HIP_TRY(hipEventCreateWithFlags(&c->rs_ev, hipEventDisableTiming));
-    const size_t bytes = sizeof(ekf::CopySeg) * table.size();
+    const size_t bytes = sizeof(Seg) * table.size();
     int rc = pinned_reserve(c->rs_pin, bytes);
     if (rc) return rc;
     memcpy(c->rs_pin.host, table.data(), bytes);
     rc = rs_wait(c);
     if (rc) return rc;
-    HIP_TRY(launch(reinterpret_cast<const ekf::CopySeg*>(c->rs_pin.dev), (int)table.size()));
+    HIP_TRY(launch(reinterpret_cast<const Seg*>(c->rs_pin.dev), (int)table.size()));
     HIP_TRY(hipEventRecord(c->rs_ev, c->stream));
     c->rs_pending = 1;
     return EKF_OK;
@@ -119,6 +121,41 @@ extern "C" int ekf_copy_instance(ekf_ctx* c, int dst, int from)
     return ekf_resample(c, src.data());
 }
 
+// ---- the device forms: the plan and the copy under a list in device memory ----
+extern "C" int ekf_resample_plan_device(ekf_ctx* c, const double* d_weights, double u, double ess_below, int32_t* d_src,
+                                        ekf_plan_info* d_info)
+{
+    if (!c || !d_weights || !d_src || c->sh_world > 0 || ess_below != ess_below) return EKF_EINVAL;
+    if (!(u >= 0.0 && u < 1.0)) return EKF_ERANGE;
+    HIP_TRY(ekf::launch_resample_plan(d_weights, c->cfg.instances, u, ess_below, d_src, d_info, c->stream));
+    return EKF_OK;
+}
+
+// ekf_resample with the list on the device: the pieces of one instance's slices go into the pinned table,
+// a wave checks the list and the copy applies the pieces to the pairs it found (unit_resample_device.hip).
+// The hazards are ekf_resample's (rs_wait before, end_read behind). What the host mirrors of the
+// overwritten instances becomes stale as a whole: it cannot know which they are.
+extern "C" int ekf_resample_device(ekf_ctx* c, const int32_t* d_src, int32_t* d_status)
+{
+    if (!c || !d_src || c->sh_world > 0) return EKF_EINVAL;
+    if (c->predicted) return EKF_EINVAL;   // the committed strip is the predicted one
+    const int E = c->cfg.instances;
+    if (!c->rsd_plan) {
+        void* pl = nullptr;
+        if (!dev_alloc(c, &pl, sizeof(int32_t) * ekf::resample_device_plan_words(E))) return EKF_ENOMEM;
+        c->rsd_plan = (int32_t*)pl;
+    }
+    const std::vector<ekf::CopyPiece> pieces = ekf::resample_pieces(ekf::resample_arrays(resample_layout(c)));
+    int rc = run_table(c, pieces, [c, d_src, d_status, E](const ekf::CopyPiece* t, int n) {
+        return ekf::launch_resample_device(d_src, E, c->rsd_plan, d_status, t, n, c->ncu, c->stream);
+    });
+    if (!rc) rc = end_read(c);
+    if (rc) return rc;
+    c->pexp_stale = 1;     // (pexp_mirror)
+    c->mirror_epoch = 0;   // the mirrored robot blocks are stale for the overwritten instances
+    return EKF_OK;
+}
+
 // ---- instance images ----
 // The arrays of ekf_resample in logical order, one instance of each as a 16-byte padded section.
 // Nothing of the schedule changes in either direction; the import maps the sections onto this
@@ -154,8 +191,10 @@ static int image_args(const ekf_ctx* c, const int32_t* inst, int K, const void* 
     return EKF_OK;
 }
 
-static void image_describe(const ekf_ctx* c, const int32_t* inst, int K, uint64_t bytes, ekf_image_desc* desc)
+static int image_describe(ekf_ctx* c, const int32_t* inst, int K, uint64_t bytes, ekf_image_desc* desc)
 {
+    const int rc = pexp_mirror(c);   // (storage_exp below)
+    if (rc) return rc;
     const uint64_t key = image_key_of(c);
     for (int k = 0; k < K; k++) {
         ekf_image_desc& d = desc[k];
@@ -170,6 +209,7 @@ static void image_describe(const ekf_ctx* c, const int32_t* inst, int K, uint64_
         d.groups = c->last_G;
         d.storage_exp = c->pexp_h[inst[k]];
     }
+    return EKF_OK;
 }
 
 // import: the list names no slot twice and every descriptor is congruent with this context
@@ -223,8 +263,7 @@ extern "C" int ekf_export_instances(ekf_ctx* c, const int32_t* inst, int K, void
             memset(q + s.bytes, 0, (size_t)(ekf::image_pad16(s.bytes) - s.bytes));
         }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    image_describe(c, inst, K, bytes, desc);
-    return EKF_OK;
+    return image_describe(c, inst, K, bytes, desc);
 }
 
 extern "C" int ekf_import_instances(ekf_ctx* c, const int32_t* inst, int K, const void* images,
@@ -270,8 +309,8 @@ extern "C" int ekf_export_instances_device(ekf_ctx* c, const int32_t* inst, int 
     const std::vector<ekf::CopySeg> table = ekf::image_export_plan(arrays, inst, K, (uint64_t)(uintptr_t)d_images);
     rc = run_image_table(c, table);
     if (rc) return rc;
-    image_describe(c, inst, K, ekf::image_bytes(arrays), desc);
-    return end_read(c);
+    rc = image_describe(c, inst, K, ekf::image_bytes(arrays), desc);
+    return rc ? rc : end_read(c);
 }
 
 extern "C" int ekf_import_instances_device(ekf_ctx* c, const int32_t* inst, int K, const void* d_images,

@@ -72,6 +72,11 @@ struct ekf_ctx {
     PinnedBuf rs_pin;
     hipEvent_t rs_ev = nullptr;
     int rs_pending = 0;
+    // ekf_resample_device: the checked list the copy reads (kernels.h resample_device_plan_words; listed
+    // context memory, made on first use). The call cannot update pexp_h, so it marks it stale and the
+    // readers of pexp_h re-read the device array first (pexp_mirror)
+    int32_t* rsd_plan = nullptr;
+    int pexp_stale = 0;
     // partitioned instance (ekf_shard_create): rank sh_rank of sh_world stores tile rows [sh_r0, sh_r1);
     // the running scan's replicated state
     int sh_rank = -1, sh_world = 0, sh_r0 = 0, sh_r1 = 0;
@@ -226,6 +231,7 @@ int drain(ekf_ctx* c);           // flushes the partial group, waits for S and D
 int enqueue_flush(ekf_ctx* c);   // one flush of the steps [unflushed0, nsteps), if any (who adds a step calls it at T)
 void fill_results(const ekf_ctx* c, ekf_result* out);   // out[E] (or null) from the host copies h_res, h_pose
 int strip_copy(ekf_ctx* c, int e, int* cb);   // waits for S; *cb: instance e's committed strip and mean, 0 or 1
+int pexp_mirror(ekf_ctx* c);     // before reading pexp_h: if a device-side resample left it stale, waits for S and re-reads pexp
 int set_robot_ctor(ekf_ctx* c, int e, double x, double y, double th);   // (ekf_state.hip) Robot::Robot; waits for S
 void rccl_destroy(ekf_ctx* c);   // (ekf_shard.hip) the context's communicator, if it has one
 #pragma GCC visibility pop

@@ -412,6 +412,22 @@ hipError_t launch_resample(const CopySeg* table, int nseg, int ncu, hipStream_t 
 // ekf_image_plan.h, dealt the same way; dst_epoch: the importing context's launch epoch, which the
 // re-tag pieces give the completion words
 hipError_t launch_image(const CopySeg* table, int nseg, unsigned dst_epoch, int ncu, hipStream_t st);
+// ekf_resample_device (unit_resample_device.hip): the list src [E] is device memory. One wave checks it
+// and writes [count, status, (dst, src) × count] to plan (resample_device_plan_words(E) ints of context
+// scratch) and the status to *status (may be null); the copy applies the pieces of one instance's slices
+// (resample_pieces, device-readable) to those pairs, under launch_resample's grid cap
+struct CopyPiece;
+size_t resample_device_plan_words(int E);
+hipError_t launch_resample_device(const int32_t* src, int E, int32_t* plan, int32_t* status, const CopyPiece* pieces,
+                                  int npieces, int ncu, hipStream_t st);
+// The small stages of the hypothesis loop (unit_loop.hip; slam_ekf.h ekf_gate_candidates_device,
+// ekf_assoc_weights_device, ekf_resample_plan_device): device buffers, no filter state, one launch each
+hipError_t launch_gate_candidates(const double* d2, const int32_t* nlines, int E, int max_lines, int N, int C,
+                                  double gate, int32_t* cand, int32_t* count, hipStream_t st);
+hipError_t launch_assoc_weights(const ekf_assoc_hit* hits, const int32_t* nlines, int E, double log_unassigned,
+                                const double* logprior, double* weights, hipStream_t st);
+hipError_t launch_resample_plan(const double* weights, int E, double u, double ess_below, int32_t* src,
+                                ekf_plan_info* info, hipStream_t st);
 
 hipError_t launch_scan(const ScanParams& p, int precision, hipStream_t st);
 int scan_blocks_per_cu(int precision);

@@ -1,7 +1,8 @@
 // ekf_read.hip — the calls that read the state without draining the flush (slam_ekf.h): the covariance
 // queries (ekf_query_*; kernel: unit_query.hip), the gate (ekf_gate_lines*; unit_gate.hip), the joint
 // gate (ekf_gate_joint*; unit_joint.hip) and the joint-compatibility search (ekf_associate_joint*;
-// unit_assoc.hip).
+// unit_assoc.hip). Beside them the two stages of the hypothesis loop that read only what those calls wrote
+// (ekf_gate_candidates_device, ekf_assoc_weights_device; unit_loop.hip): no view, no hazard handling.
 //
 // Each kernel takes the view the next association kernel would take in enqueue() (ReadView): X[base]
 // once the event guarding it has passed, the steps [pend0, nsteps) applied on read, the committed copy
@@ -415,4 +416,25 @@ extern "C" int ekf_associate_joint_device(ekf_ctx* c, const double* d_enc, const
     ap.cand = d_cand;
     ap.hits = d_hits;
     return enqueue_assoc(c, ap);
+}
+
+// ---- the loop's stages around the search: functions of the gate's matrix and of the hits, no filter state ----
+extern "C" int ekf_gate_candidates_device(ekf_ctx* c, const double* d_d2, const int32_t* d_nlines, int C, double gate,
+                                          int32_t* d_cand, int32_t* d_count)
+{
+    if (!c || c->sh_world > 0 || !d_d2 || !d_nlines || !d_cand) return EKF_EINVAL;
+    if (!(gate >= 0.0) || gate - gate != 0.0) return EKF_EINVAL;   // NaN, negative, +inf
+    if (C < 1 || C > EKF_ASSOC_MAX_CAND) return EKF_ERANGE;
+    HIP_TRY(ekf::launch_gate_candidates(d_d2, d_nlines, c->cfg.instances, c->d.max_lines, c->d.N, C, gate, d_cand,
+                                        d_count, c->stream));
+    return EKF_OK;
+}
+
+extern "C" int ekf_assoc_weights_device(ekf_ctx* c, const ekf_assoc_hit* d_hits, const int32_t* d_nlines,
+                                        double log_unassigned, const double* d_logprior, double* d_weights)
+{
+    if (!c || c->sh_world > 0 || !d_hits || !d_nlines || !d_weights) return EKF_EINVAL;
+    HIP_TRY(ekf::launch_assoc_weights(d_hits, d_nlines, c->cfg.instances, log_unassigned, d_logprior, d_weights,
+                                      c->stream));
+    return EKF_OK;
 }

@@ -1,7 +1,9 @@
 // ekf_resample_plan.h — the copy table of ekf_resample (slam_ekf.h): which bytes instance e takes
 // from instance src[e]. Host only (no HIP include): ekf_copy.hip fills a ResampleLayout from the
 // context and hands the table to launch_resample (unit_resample.hip); tests/cpp/resample_driver.cpp
-// checks it on a CPU.
+// checks it on a CPU. ekf_resample_device, whose list is device memory, takes resample_pieces instead:
+// the same arrays cut into the same pieces, without the instances (kernel: unit_resample_device.hip;
+// checked by tests/cpp/loop_driver.cpp).
 //
 // Everything an instance owns is a slice of an array laid out [E][slice] (the two copies of the
 // robot strip, the mean and the diagonal blocks are two such arrays each), so the state of an
@@ -158,6 +160,34 @@ inline std::vector<CopySeg> resample_plan(const std::vector<ResampleArray>& arra
                 const uint64_t len = a.bytes - off < chunk ? a.bytes - off : chunk;
                 t.push_back(CopySeg{s + off, q + off, (uint32_t)len, cls});
             }
+        }
+    }
+    return t;
+}
+
+// ekf_resample_device's table: the list lives on the device, so the host lists the pieces of one
+// instance's slices and the kernel applies each to every (src[e], e) it finds: bytes [off, off + len) of
+// slice src[e] of the array at `base` onto the same bytes of slice e. cls comes from base | slice, which is
+// resample_class for every pair of instances (the slice length enters both, and with it every distance
+// between two slices).
+struct CopyPiece {
+    uint64_t base, slice;   // the array and its bytes per instance
+    uint64_t off;           // of the piece in the slice
+    uint32_t len;           // at most `chunk`
+    uint32_t cls;
+};
+
+inline std::vector<CopyPiece> resample_pieces(const std::vector<ResampleArray>& arrays, uint32_t chunk = RS_CHUNK)
+{
+    std::vector<CopyPiece> t;
+    size_t pieces = 0;
+    for (const ResampleArray& a : arrays) pieces += (size_t)((a.bytes + chunk - 1) / chunk);
+    t.reserve(pieces);
+    for (const ResampleArray& a : arrays) {
+        const uint32_t cls = resample_class(a.base, a.base, a.bytes);
+        for (uint64_t off = 0; off < a.bytes; off += chunk) {
+            const uint64_t len = a.bytes - off < chunk ? a.bytes - off : chunk;
+            t.push_back(CopyPiece{a.base, a.bytes, off, (uint32_t)len, cls});
         }
     }
     return t;

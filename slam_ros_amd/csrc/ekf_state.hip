@@ -11,12 +11,14 @@
 // Every entry point that writes an instance's state without a scan (reset, upload, low-rank
 // initialisation, rescale, and any added later) starts here: the synchronous calls' result mirror
 // holds the robot block of the last scan, which the write makes stale (ekf_get_pose_cov must not
-// serve it), and the write needs the materialised landmark block.
+// serve it), and the write needs the materialised landmark block. The writers read or replace single
+// storage exponents of the host's copy: it is brought up to date first (pexp_mirror).
 static int begin_state_write(ekf_ctx* c)
 {
     c->mirror_epoch = 0;
     c->predicted = 0;
-    return drain(c);
+    const int rc = drain(c);
+    return rc ? rc : pexp_mirror(c);
 }
 
 // ... and a writer of instance e's strip, mean or landmark block goes on with the committed copy, *cb
@@ -156,6 +158,7 @@ extern "C" int ekf_download_state(ekf_ctx* c, int e, double* P, double* y, int* 
     int rc = EKF_OK;
     if (P) rc = drain(c);
     else HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!rc && P) rc = pexp_mirror(c);
     if (rc) return rc;
     const Dims& d = c->d;
     int cb = 0;
@@ -222,6 +225,8 @@ extern "C" int ekf_storage_exponent(const ekf_ctx* c, int e)
 {
     if (!c) return 0;
     if (e < 0 || e >= c->cfg.instances) return 0;
+    // (after ekf_resample_device the host's copy is re-read from the device: a wait for the stream)
+    if (pexp_mirror(const_cast<ekf_ctx*>(c)) != EKF_OK) return 0;
     return c->pexp_h[e];
 }
 

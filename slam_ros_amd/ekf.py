@@ -46,6 +46,7 @@ EXPORTED = [
     "ekf_gate_lines", "ekf_gate_lines_device", "ekf_gate_joint", "ekf_gate_joint_device",
     "ekf_associate_joint", "ekf_associate_joint_device",
     "ekf_resample", "ekf_copy_instance",
+    "ekf_gate_candidates_device", "ekf_assoc_weights_device", "ekf_resample_plan_device", "ekf_resample_device",
     "ekf_instance_image_bytes", "ekf_export_instances", "ekf_import_instances",
     "ekf_export_instances_device", "ekf_import_instances_device",
     "ekf_landmark_block_bytes",
@@ -116,6 +117,19 @@ class EkfAssocHit(ctypes.Structure):
 
 
 ekf_assoc_hit = EkfAssocHit   # (the C name)
+
+
+RP_INVALID, RP_KEPT = 1, 2   # ekf_plan_info.status
+
+
+class EkfPlanInfo(ctypes.Structure):
+    """ekf_plan_info (slam_ekf.h): what ekf_resample_plan_device reports beside its list."""
+    _fields_ = [
+        ("status", ctypes.c_int32), ("copies", ctypes.c_int32), ("ess", ctypes.c_double), ("total", ctypes.c_double),
+    ]
+
+
+ekf_plan_info = EkfPlanInfo   # (the C name)
 
 
 class EkfImageDesc(ctypes.Structure):
@@ -194,6 +208,10 @@ def load_library(path: str = ""):
         "ekf_associate_joint_device": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]),
         "ekf_resample": (ctypes.c_int, [vp, ip]),
         "ekf_copy_instance": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
+        "ekf_gate_candidates_device": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, d, vp, vp]),
+        "ekf_assoc_weights_device": (ctypes.c_int, [vp, vp, vp, d, vp, vp]),
+        "ekf_resample_plan_device": (ctypes.c_int, [vp, vp, d, d, vp, vp]),
+        "ekf_resample_device": (ctypes.c_int, [vp, vp, vp]),
         "ekf_instance_image_bytes": (sz, [vp]),
         "ekf_export_instances": (ctypes.c_int, [vp, ip, ctypes.c_int, vp, vp]),
         "ekf_import_instances": (ctypes.c_int, [vp, ip, ctypes.c_int, vp, vp]),
@@ -635,6 +653,41 @@ class Ensemble:
         if sa.size != self.instances:
             raise ValueError(f"resample: {sa.size} sources for {self.instances} instances")
         _check(self._lib.ekf_resample(self._h, sa.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "ekf_resample")
+
+    def gate_candidates_device(self, d_d2: int, d_nlines: int, C: int, gate: float, d_cand: int, d_count: int = 0):
+        """gate_candidates on the device, for every line of every instance (slam_ekf.h
+        ekf_gate_candidates_device; raw pointers: d2 [E, max_lines, N] as gate_lines_device wrote it, nlines
+        [E] int32, cand [E, max_lines, C] int32, count [E, max_lines] int32 or 0: the members before the
+        cut). The lists are gate_candidates' bit for bit; asynchronous on the context stream."""
+        _check(self._lib.ekf_gate_candidates_device(self._h, ctypes.c_void_p(d_d2 or None), ctypes.c_void_p(d_nlines or None),
+                                                    int(C), float(gate), ctypes.c_void_p(d_cand or None),
+                                                    ctypes.c_void_p(d_count or None)), "ekf_gate_candidates_device")
+
+    def assoc_weights_device(self, d_hits: int, d_nlines: int, d_weights: int, log_unassigned: float = 0.0,
+                             d_logprior: int = 0):
+        """The instances' weights from associate_joint_device's hits (ekf_assoc_weights_device; raw
+        pointers: hits [E] ekf_assoc_hit, nlines [E] int32, weights [E], logprior [E] or 0):
+        exp(lw - max lw) with lw = -(d2 + logdet) / 2 - m log(2 pi) + (nlines - m) log_unassigned + logprior;
+        0 for an instance whose hit is AS_INVALID or whose lw is not finite. Asynchronous."""
+        _check(self._lib.ekf_assoc_weights_device(self._h, ctypes.c_void_p(d_hits or None), ctypes.c_void_p(d_nlines or None),
+                                                  float(log_unassigned), ctypes.c_void_p(d_logprior or None),
+                                                  ctypes.c_void_p(d_weights or None)), "ekf_assoc_weights_device")
+
+    def resample_plan_device(self, d_weights: int, u: float, d_src: int, ess_below: float = math.inf, d_info: int = 0):
+        """resample_plan on the device (ekf_resample_plan_device; raw pointers: weights [E], src [E] int32,
+        info one ekf_plan_info or 0): the list resample_device takes. The identity list when the effective
+        sample size is not below ess_below (RP_KEPT) or the weights are unusable (RP_INVALID).
+        Asynchronous."""
+        _check(self._lib.ekf_resample_plan_device(self._h, ctypes.c_void_p(d_weights or None), float(u), float(ess_below),
+                                                  ctypes.c_void_p(d_src or None), ctypes.c_void_p(d_info or None)),
+               "ekf_resample_plan_device")
+
+    def resample_device(self, d_src: int, d_status: int = 0):
+        """resample with the list in device memory (ekf_resample_device; raw pointers: src [E] int32,
+        status one int32 or 0). The list is checked on the device: a list resample would refuse copies
+        nothing and leaves EKF_EINVAL or EKF_ERANGE in status. Asynchronous on the context stream."""
+        _check(self._lib.ekf_resample_device(self._h, ctypes.c_void_p(d_src or None), ctypes.c_void_p(d_status or None)),
+               "ekf_resample_device")
 
     def copy_instance(self, dst: int, src: int):
         """Instance dst becomes a copy of instance src (ekf_copy_instance): forks a hypothesis."""
