@@ -82,7 +82,9 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-mllvm", "-amdgpu-mfma-vgpr-for
 # unit_*.hip includes the device code its kernels need (the flush units a header per flush family,
 # the query unit ekf_device.h alone, the gate unit ekf_gate.h, the joint and search units
 # ekf_joint_parts.h above it, the resample and image units only their tables' headers and the shared
-# copy body, the loop unit ekf_loop_plan.h alone, the others the association kernels, ekf_kernels.hip, which is not compiled on its own)
+# copy body, the loop unit ekf_loop_plan.h alone, the three scan units the association kernel, ekf_kernels.hip,
+# which is not compiled on its own, and unit_shard_pack.hip the partitioned instance's kernels,
+# ekf_shard_kernels.h, with ekf_pack.h; those two share ekf_assoc_parts.h)
 # and defines the launchers that instantiate them; they compile in parallel with the five host units,
 # which define no kernels and share ekf_ctx.h: ekf_api.hip (the context and the schedule), ekf_state.hip
 # (state transfers, ellipse), ekf_shard.hip (the partitioned instance, RCCL), ekf_read.hip (queries, gate,

@@ -477,7 +477,8 @@ extern "C" int ekf_shard_create(const ekf_config* cfg, int rank, int world, ekf_
     // wave flushes take (fp32 <= 8 steps, fp64 <= 8)
     if (world < 1 || rank < 0 || rank >= world || cfg->instances != 1 || cfg->pipeline ||
         cfg->arith != EKF_ARITH_EXACT || (cfg->precision != EKF_PREC_F32 && cfg->precision != EKF_PREC_F64) ||
-        cfg->flush_interval > (cfg->precision == EKF_PREC_F64 ? ekf::F64_WAVE_MAXS : 8) || cfg->max_lines > 8)
+        cfg->flush_interval > (cfg->precision == EKF_PREC_F64 ? ekf::F64_WAVE_MAXS : 8) ||
+        cfg->max_lines > ekf::SH_MAX_LINES)
         return EKF_EINVAL;
     return create_ctx(cfg, rank, world, out);
 }

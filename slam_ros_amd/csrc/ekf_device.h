@@ -25,8 +25,10 @@
 // the MFMA executes, then the patch rounded to storage, so every read sees bit-for-bit the value
 // the flush will store (tests/test_gpu_parity.py::test_deferred_flush_equals_drained).
 //
-// The device code by topic: ekf_kernels.hip (the association: its arithmetic, the exchange, scan_kernel,
-// the partitioned instance), ekf_gate.h (the gate arithmetic of one candidate, shared with the gate
+// The device code by topic: ekf_kernels.hip (the association: scan_kernel and what only it uses),
+// ekf_shard_kernels.h (the kernels of an instance partitioned over ranks), ekf_assoc_parts.h (what those
+// two share: the reject filters, the exchange, the gain chain of a match), ekf_gate.h (the gate
+// arithmetic of one candidate, shared with the gate
 // query), ekf_flush_common.h and one ekf_flush_*.h per flush family, ekf_pack.h;
 // unit_query.hip holds the covariance queries' kernel (pll_block on chosen landmarks), unit_gate.hip
 // the gate query's two kernels (trial lines against every saved landmark, state untouched),

@@ -1,7 +1,7 @@
 // ekf_gate.h — the gate arithmetic of the association (Robot.cpp:313-498): the 5×5 block of a
 // candidate, its innovation covariance and innovation, the exact fp64 evaluation with the gate
-// decision and the storage precision of the gate. Shared by the association kernels (ekf_kernels.hip)
-// and the gate queries (unit_gate.hip, unit_joint.hip: trial_robot, trial_block), so that all evaluate a
+// decision and the storage precision of the gate. Shared by the association kernels (ekf_kernels.hip,
+// ekf_shard_kernels.h) and the gate queries (unit_gate.hip, unit_joint.hip: trial_robot, trial_block), so that all evaluate a
 // candidate bit for bit alike.
 #pragma once
 

@@ -30,9 +30,8 @@ constexpr int F16_EXP_DEFAULT = 10;
 enum { SYNC_START = 0, SYNC_WG0 = 4 };
 constexpr int MAX_GROUPS = (MAX_CAPACITY + SCAN_THREADS - 1) / SCAN_THREADS;   // workgroups per instance
 constexpr int SPEC_GMAX = 64;  // speculative association: workgroups per instance (<= one wave)
-constexpr int MB_WORDS_FIXED = 26; // mailbox words before the V-history (see ekf_kernels.hip)
+constexpr int MB_WORDS_FIXED = 26; // mailbox words before the V-history (see ekf_assoc_parts.h)
 constexpr int SH_MAX_LINES = 8;     // a partitioned context's lines per scan (ekf_shard_create)
-constexpr int SH_PKG_WORDS = MB_WORDS_FIXED + 4 * SH_MAX_LINES;   // one gain package of its scan
 
 // per-instance result record in device memory (ints)
 enum {
@@ -142,10 +141,11 @@ struct ScanParams {
 // the diagonal blocks once per scan, the winner's column once per matched line.
 enum { SH_BEGIN = 0, SH_DIAG = 1, SH_GATE = 2, SH_COLUMN = 3, SH_APPLY = 4, SH_ROBOT = 5, SH_END = 6,
        // speculative association of the partitioned instance (ekf_shard_speculate / ekf_shard_run):
-       // every line's first passing landmark at the scan's start (the guesses), the rank's blocks of
-       // all guessed columns, and (shard_run_kernel) the winner's package without its column
-       SH_GUESS = 7, SH_SPEC_COLS = 8, SH_PACKAGE = 9 };
+       // every line's first passing landmark at the scan's start (the guesses) and the rank's blocks of
+       // all guessed columns
+       SH_GUESS = 7, SH_SPEC_COLS = 8 };
 constexpr int SH_REC = 20;   // doubles per landmark: rr0..2 (6), yb (2), Dj (4), ma0, s0j, c0j, s0f, c0f, spare
+                             // (the words by name: ekf_shard_kernels.h, REC_*)
 // device control words of the running scan (no host round trip between phases)
 enum { SC_WIN = 0, SC_STATUS = 1, SC_M = 2, SC_NEXTRA = 3, SC_S = 4, SC_NEXT = 5, SC_MATCH = 8,
        SC_EXTRA = 8 + EKF_MAX_LINES, SC_GUESS = 8 + 2 * EKF_MAX_LINES, SC_WORDS = 8 + 3 * EKF_MAX_LINES };
@@ -172,7 +172,7 @@ struct ShardParams {
     int* ctl;             // [SC_WORDS]
     double* col;          // [N][4] the exchange buffer (caller's device memory)
     double* cols;         // [L][N][4] the guessed columns' exchange buffer (speculative path)
-    double* next_out;     // shard_run_kernel: the line it stopped at, as a double (caller's device memory)
+    double* next_out;     // shard_spec_kernel: the line it stopped at, as a double (caller's device memory)
     const double* enc;    // [3]
     const ekf_line* lines;// [max_lines]
     const int* pexp;
@@ -180,10 +180,10 @@ struct ShardParams {
     double enc_v[3];      // SH_BEGIN: the scan's encoder pose and lines (kernel arguments; it stores
     ekf_line lines_v[EKF_MAX_LINES];   // them to enc / lines for the later phases)
     int diag_first;       // SH_GUESS: take the summed diagonal blocks first (SH_DIAG in the same launch)
-    double* pkg_slot;     // SH_GATE (shard_run_kernel): a passing landmark's package into this slot
     int* res_host;        // SH_END: the step's record and pose also into pinned host memory (device
     double* pose_host;    // pointers; nullptr: not)
-    double* mbox;         // shard_run_kernel: the workgroups' mailbox (2 parities × G slots of mbw words)
+    double* mbox;         // shard_spec_kernel: its workgroups' mailbox (the verdict and outcome words; G
+                          // slots of mbw words, parity 0)
     int mbw;
     unsigned epoch;       // its tag epoch (one per launch)
     int spin_log2;        // its bounded waits
@@ -192,18 +192,16 @@ struct ShardParams {
                               // memory (device pointer) either way (nullptr: commit unconditionally)
 };
 hipError_t launch_shard(const ShardParams& p, int precision, hipStream_t st);
-// lines [ctl[SC_NEXT], L) of the speculative path on shard_run_workgroups(N) cooperating
-// workgroups (shard_run_kernel)
+// the lines of the speculative path from line 0, up to the first whose guess is wrong, on
+// shard_run_workgroups(N) cooperating workgroups (shard_spec_kernel); hipErrorInvalidValue for more
+// than SH_MAX_LINES lines, which ekf_shard_create does not admit
 hipError_t launch_shard_run(const ShardParams& p, int precision, hipStream_t st);
 constexpr int SH_THREADS = 64;     // shard_kernel's workgroup
 #ifndef EKF_SHR_THREADS
 #define EKF_SHR_THREADS 128
 #endif
-constexpr int SHR_THREADS = EKF_SHR_THREADS;   // shard_run_kernel's workgroup: landmarks per workgroup
+constexpr int SHR_THREADS = EKF_SHR_THREADS;   // shard_spec_kernel's landmark threads: landmarks per workgroup
 constexpr int SHR_GMAX = 64;       // ... and at most this many workgroups (more landmarks per thread past it)
-#ifndef EKF_SHARD_SPEC
-#define EKF_SHARD_SPEC 1           // launch_shard_run: shard_spec_kernel where it applies (0: shard_run_kernel always)
-#endif
 inline int shard_run_workgroups(int N)
 {
     const int g = (N + SHR_THREADS - 1) / SHR_THREADS;

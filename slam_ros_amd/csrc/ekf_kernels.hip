@@ -1,9 +1,9 @@
-// ekf_kernels.hip — the association kernels of the EKF-SLAM update: the association arithmetic and
-// the exchange, scan_kernel, and the kernels of an instance partitioned over ranks (the step overview:
-// ekf_device.h). Not compiled on its own: unit_scan*.hip and unit_shard_pack.hip include it and define
-// the launchers that instantiate their share of it. The gate arithmetic of a candidate is ekf_gate.h.
-#include "ekf_device.h"
-#include "ekf_gate.h"
+// ekf_kernels.hip — the association kernel of the EKF-SLAM update: scan_kernel and the helpers only
+// it uses (the step overview: ekf_device.h). Not compiled on its own: the three unit_scan*.hip include
+// it and define the launchers that instantiate their share of it. What it shares with the kernels of
+// an instance partitioned over ranks (ekf_shard_kernels.h) — the reject filters, the mailbox, the gain
+// package and rows — is ekf_assoc_parts.h; the gate arithmetic of a candidate is ekf_gate.h.
+#include "ekf_assoc_parts.h"
 
 // The association arithmetic contracts a·b + c only within one source expression, so a
 // function inlined into different kernels or phases rounds identically everywhere (the
@@ -11,128 +11,6 @@
 #pragma clang fp contract(on)
 
 namespace ekf {
-
-// Uniform per-line package published by the matching thread (LDS).
-enum {
-    C_S = 0, C_SI = 4, C_V = 8, C_H = 10, C_KR = 13, C_UR = 19, C_WORDS = 25,
-};
-
-// sin/cos of a landmark angle from those of its value at the start of the scan: the angle
-// moves by small Kalman corrections within a scan, so sin/cos(ma0 + δ) by the addition formula
-// with Taylor series in δ (|δ| <= 1/64: truncation below 1e-19), and the full fp64 sincos
-// otherwise. Every path that evaluates a candidate uses this form, so they agree bit for bit.
-__device__ __forceinline__ void sincos_near(double ma, double ma0, double s0, double c0, double& sn,
-                                            double& cs)
-{
-    const double dl = ma - ma0;
-    if (fabs(dl) <= 0.0009765625) {
-        // |δ| <= 2^-10: sin δ = δ − δ³/6 (next term ≤ 8e-18), 1 − cos δ = δ²/2 − δ⁴/24 (≤ 2e-21)
-        const double d2 = dl * dl;
-        const double sd = dl * (1.0 - d2 * (1.0 / 6.0));
-        const double cm = d2 * 0.5 * (1.0 - d2 * (1.0 / 12.0));
-        sn = s0 - (s0 * cm - c0 * sd);
-        cs = c0 - (c0 * cm + s0 * sd);
-    } else if (fabs(dl) <= 0.015625) {
-        const double d2 = dl * dl;
-        const double sd = dl * (1.0 - d2 * (1.0 / 6.0) * (1.0 - d2 * (1.0 / 20.0) * (1.0 - d2 * (1.0 / 42.0))));
-        const double cm = d2 * 0.5 * (1.0 - d2 * (1.0 / 12.0) * (1.0 - d2 * (1.0 / 30.0) * (1.0 - d2 * (1.0 / 56.0))));
-        sn = s0 - (s0 * cm - c0 * sd);   // s0·cos δ + c0·sin δ, cos δ = 1 − cm
-        cs = c0 - (c0 * cm + s0 * sd);   // c0·cos δ − s0·sin δ
-    } else {
-        sincos(ma, &sn, &cs);
-    }
-}
-
-// Certified rejection: true only if the exact evaluation is guaranteed to fail the gate. It
-// accepts sin/cos with |error| <= EPS (here the exact ones of sincos_near);
-// the resulting error in S and v is bounded explicitly and d² = q/det is bounded from below by
-// interval arithmetic. Requires a symmetric R and a determinant that is not tiny relative to
-// |S00·S11| + |S01·S10| (so that the reference's LU-based d² is within 1e-9 of q/det).
-__device__ __forceinline__ bool certified_reject(const Block5& b, double ma, double mr, double sn,
-                                                 double cs, const double xp[3], double za, double zr,
-                                                 const double Rm[4], double gate, double eta)
-{
-    if (!(fabs(ma) <= 8.0) || Rm[1] != Rm[2]) return false;
-    const double EPS = 1e-5;
-    const double h10 = -cs, h11 = -sn, h1l = xp[0] * sn - xp[1] * cs;
-    double S[4], hp0[5], hp1[5];
-    innovation_cov(b, h10, h11, h1l, Rm, S, hp0, hp1);
-    const double v0 = innovation_angle(za, ma, xp[2]);
-    const double v1 = zr - (mr - (xp[0] * cs + xp[1] * sn));
-    const double ex = EPS * (fabs(xp[0]) + fabs(xp[1]));
-    double Pm = fmax(fmax(fmax(fabs(b.p00), fabs(b.p01)), fmax(fabs(b.p02), fabs(b.p10))),
-                     fmax(fmax(fabs(b.p11), fabs(b.p12)), fmax(fabs(b.p20), fabs(b.p21))));
-    Pm = fmax(Pm, fmax(fmax(fmax(fabs(b.p22), fabs(b.p0a)), fmax(fabs(b.p1a), fabs(b.p2a))),
-                       fmax(fmax(fabs(b.p0b), fabs(b.p1b)), fabs(b.p2b))));
-    Pm = fmax(Pm, fmax(fmax(fabs(b.daa), fabs(b.dab)), fmax(fabs(b.dba), fabs(b.dbb))));
-    const double dh = (2.0 * EPS + ex) * Pm;                   // |Δ hp1[b]|
-    // + the storage precision of the gate (gate_eta)
-    const double m0 = eta * 2.0 * (fabs(b.p22) + fabs(b.daa));
-    const double m1 = eta * (2.0 + (fabs(h1l) + ex) * (fabs(h1l) + ex)) *
-                      (fabs(b.p00) + fabs(b.p11) + fabs(b.p22) + fabs(b.daa) + fabs(b.dbb));
-    const double dS00 = m0;
-    const double dS01 = EPS * (fabs(hp0[0]) + fabs(hp0[1])) + ex * fabs(hp0[3]) + 0.5 * (m0 + m1);
-    const double dS10 = 2.0 * dh + 0.5 * (m0 + m1);
-    const double dS11 = dh * (3.0 + fabs(h1l) + ex) + EPS * (fabs(hp1[0]) + fabs(hp1[1])) +
-                        ex * fabs(hp1[3]) + m1;
-    const double dv1 = ex;
-    const double q = v0 * v0 * S[3] - v0 * v1 * (S[1] + S[2]) + v1 * v1 * S[0];
-    const double det = S[0] * S[3] - S[1] * S[2];
-    const double mag_det = fabs(S[0] * S[3]) + fabs(S[1] * S[2]);
-    const double mag_q = v0 * v0 * fabs(S[3]) + fabs(v0 * v1) * (fabs(S[1]) + fabs(S[2])) +
-                         v1 * v1 * fabs(S[0]);
-    const double av1 = fabs(v1) + dv1;
-    const double dq = v0 * v0 * dS11 + fabs(v0) * av1 * (dS01 + dS10) +
-                      fabs(v0) * dv1 * fabs(S[1] + S[2]) +
-                      (2.0 * fabs(v1) * dv1 + dv1 * dv1) * fabs(S[0]) + av1 * av1 * dS00 + 1e-9 * mag_q;
-    const double ddet = fabs(S[0]) * dS11 + fabs(S[3]) * dS00 + fabs(S[1]) * dS10 + fabs(S[2]) * dS01 +
-                        dS01 * dS10 + dS00 * dS11 + 1e-9 * mag_det;
-    const double det_lo = det - ddet;
-    if (!(det_lo > 1e-6 * mag_det)) return false;              // also false for NaN / Inf
-    return (q - dq) > gate * gate * (1.0 + 1e-6) * (det + ddet);
-}
-
-// Certified cheap rejection (the first filter of the per-line gate: ≈35 fp64 operations, no
-// trigonometry). For a symmetric positive definite S, vᵀS⁻¹v ≥ v0²/S00 and vᵀS⁻¹v ≥ v1²/S11, so
-// the exact evaluation fails the gate (Robot.cpp:489) if either one-dimensional bound exceeds it:
-//  * S00 = H0·P5·H0ᵀ + R00 with the constant row H0 = (0, 0, −1, 1, 0): p22 − 2·p2a + daa + R00
-//    (innovation_cov's S[0]); the reference's normalizeRadian (Robot.cpp:62-71) and the 2π fold
-//    (:465-475) shift za − (ma − x_pre2) by multiples of 2π only, so |v0| ≥ its circular distance
-//    to 0;
-//  * S11 = H1·P5·H1ᵀ + R11 ≤ ‖H1‖²·tr(P5) + R11 with ‖H1‖² = 2 + h1l² ≤ 2 + (|x0| + |x1|)² (P5,
-//    a principal block of a covariance, is positive semidefinite); v1 = zr − (mr − (x0·cos ma +
-//    x1·sin ma)) bounded from below with the scan-start sin/cos of ma0 (|Δcos|, |Δsin| ≤ |ma − ma0|).
-// It needs R symmetric with R00, R11 large against the storage rounding of P5 (which could
-// otherwise make S indefinite: then it never rejects) and finite inputs (NaN never rejects).
-// Margins: 1e-6 relative on the gate plus absolute slack, far above the rounding of the bounds
-// and of the exact evaluation.
-// s0, c0: sin/cos of ma0 within QR_TRIG_EPS (the fp32 __sincosf of (float)ma0 for |ma0| <= 8:
-// argument rounding <= 8·2^-24 plus the instruction's own error, ≈1e-6 together).
-constexpr double QR_TRIG_EPS = 4e-6;
-__device__ __forceinline__ bool quick_reject(const Block5& b, double ma, double mr, double ma0, double s0,
-                                             double c0, const double xp[3], double za, double zr,
-                                             const double Rm[4], double gate, double eta)
-{
-    // every bound evaluated, the tests combined without branches (bitwise on bools): the same
-    // values as the early-exit form, fewer exec-mask instructions on the per-line chain
-    const double tr5 = b.p00 + b.p11 + b.p22 + b.daa + b.dbb;
-    const double X = fabs(xp[0]) + fabs(xp[1]);
-    const double H2 = 2.0 + X * X;   // ≥ ‖H1‖²
-    const bool ok = (Rm[1] == Rm[2]) & (tr5 >= 0.0) & (Rm[0] > 1e-5 * 2.0 * tr5) & (Rm[3] > 1e-5 * H2 * tr5) &
-                    (fabs(ma0) <= 8.0);
-    const double g2 = gate * gate * (1.0 + 1e-6);
-    // S00 + its storage precision (gate_eta): |Δ(p22 − 2·p2a + daa)| <= 2·eta·(|p22| + |daa|)
-    const double S00 = b.p22 - 2.0 * b.p2a + b.daa + Rm[0] + 2.0 * eta * (fabs(b.p22) + fabs(b.daa));
-    const double x = za - (ma - xp[2]);
-    const double cd = fabs(x - 2.0 * EKF_PI * rint(x * (0.5 / EKF_PI)));
-    const double a0 = cd - 1e-12 * (1.0 + fabs(x));
-    const bool r0 = (S00 > 0.0) & (a0 > 0.0) & (a0 * a0 > g2 * S00);
-    const double v1e = zr - (mr - (xp[0] * c0 + xp[1] * s0));
-    const double a1 = fabs(v1e) - X * (fabs(ma - ma0) + QR_TRIG_EPS) - 1e-12 * (1.0 + fabs(zr) + fabs(mr) + X);
-    const double S11u = H2 * tr5 * (1.0 + 1e-5 + eta) + Rm[3];
-    const bool r1 = (a1 > 0.0) & (a1 * a1 > g2 * S11u);
-    return ok & (r0 | r1);
-}
 
 // Certified rejection in fp32 (the second filter of the per-line gate; certified_reject in fp64
 // and the exact evaluation run only where it cannot decide). Same bound structure as
@@ -248,88 +126,8 @@ __device__ __forceinline__ int st_lines(int packed, int upto)   // the bits of l
 // Thread (g, tid) of instance e OWNS landmark j = 256·g + tid: its gating candidate, its two
 // rows of W/K/U/y, its robot-strip columns and its 2×2 diagonal block, all kept in registers
 // for the whole scan. The robot 3×3 block and x_pre are uniform and recomputed identically by
-// every thread. The instance's workgroups exchange words through a mailbox (one slot per
-// workgroup and parity), written with 8-byte agent-scope atomic stores, drained by s_waitcnt
-// and a workgroup barrier before a data-tagged word (launch epoch, phase code, payload) that
-// the readers poll (MI355X_MICROARCH.md "Valid forms"). Every spin is bounded; a timeout sets a
-// status bit.
-__device__ __forceinline__ void mb_store(double* p, double v)
-{
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ double mb_load(const double* p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// mailbox slot words (the package words double as the LDS package layout)
-enum { MB_BEST = 0, MB_S = 1, MB_SI = 5, MB_V = 9, MB_H = 11, MB_KR = 14, MB_UR = 20, MB_VH = 26 };
-
-// tag word: bits 63..32 launch epoch, 31..24 phase code, 23..0 payload. Codes 1..64 are the
-// lines of the sequential association; the speculative exchanges use their own codes.
-enum { TAG_SPEC_LISTS = 0x81, TAG_SPEC_WINNERS = 0x82, TAG_SPEC_VERDICT = 0x83 };
-
-__device__ __forceinline__ void mb_tag(double* slot, unsigned epoch, unsigned code, unsigned payload)
-{
-    const unsigned long long want = ((unsigned long long)epoch << 8) | code;
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(slot + MB_BEST), (want << 24) | payload,
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Thread k < G polls workgroup k's tag of the given parity until it carries (epoch, code);
-// returns its payload (-1 on timeout, with the status bit set).
-// Every wait gives up after 2^spin polls (≈0.5 s at 24) and sets the timeout bit; a thread whose
-// status already holds it does not wait again (the launch is rolled back anyway).
-__device__ __forceinline__ int mb_poll(const double* mbox, int par, int G, int k, int mbw,
-                                       unsigned epoch, unsigned code, int& status, int spin)
-{
-    const unsigned long long want = ((unsigned long long)epoch << 8) | code;
-    const unsigned long long* tw =
-        reinterpret_cast<const unsigned long long*>(mbox + ((size_t)par * G + k) * mbw + MB_BEST);
-    unsigned long long v = __hip_atomic_load(tw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int polls = 0;
-    while ((v >> 24) != want) {
-        __builtin_amdgcn_s_sleep(1);
-        if ((status & EKF_ST_TIMEOUT_BIT) || ++polls > (1 << spin)) {   // a workgroup never arrived
-            status |= EKF_ST_TIMEOUT_BIT;
-            return -1;
-        }
-        v = __hip_atomic_load(tw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return (int)(v & 0xffffffu);
-}
-
-// Speculative list words carry their own tag: bits 63..40 the launch epoch (mod 2^24), bits
-// 39..0 the payload, written with one 8-byte atomic store, so a reader needs one poll of the word
-// itself (no separate tag word and second load). They live in the last 16 words of each
-// workgroup's parity-0 mailbox slot (MB_LIST_BACK), which nothing else writes, and every
-// speculative launch rewrites all SPEC_L of them.
-constexpr int LIST_TAG_SHIFT = 40;
-constexpr int MB_LIST_BACK = 16;
-
-__device__ __forceinline__ void mb_store_tagged(double* p, unsigned epoch, unsigned long long payload)
-{
-    const unsigned long long w = ((unsigned long long)(epoch & 0xffffffu) << LIST_TAG_SHIFT) | payload;
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ unsigned long long mb_wait_tagged(const double* p, unsigned epoch, int& status, int spin)
-{
-    const unsigned long long* w = reinterpret_cast<const unsigned long long*>(p);
-    const unsigned long long want = epoch & 0xffffffu;
-    unsigned long long v = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int polls = 0;
-    while ((v >> LIST_TAG_SHIFT) != want) {
-        __builtin_amdgcn_s_sleep(1);
-        if ((status & EKF_ST_TIMEOUT_BIT) || ++polls > (1 << spin)) {
-            status |= EKF_ST_TIMEOUT_BIT;
-            return 0;
-        }
-        v = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return v & ((1ull << LIST_TAG_SHIFT) - 1);
-}
+// every thread. The instance's workgroups exchange words through a mailbox (ekf_assoc_parts.h:
+// mb_store .. mb_wait_tagged). Every spin is bounded; a timeout sets a status bit.
 
 // End of a launch (rollback protocol). Every workgroup has written its owned columns of the
 // robot strip and mean into the inactive copy; it publishes its completion word (done_word) after
@@ -384,196 +182,6 @@ __device__ __forceinline__ int lead_collect(int* sync, int G, unsigned epoch, in
     }
     zg = z;
     return st;
-}
-
-// Symmetric downdate operands (fp32 operand storage, every mode but the reference's asymmetric
-// R): the landmark block's share of P −= K·S·Kᵀ (Robot.cpp:560-568) is stored as U·Vᵀ with
-// V = K·F and U = −2^x·V (x the fp16 storage exponent, else 0), F·Fᵀ = S: the lower Cholesky
-// factor of the symmetrised S, in fp32 like the operands themselves (a non-positive pivot
-// contributes 0, which happens only where S is singular and K = 0). Every stored element then
-// gets the same products whichever orientation is stored (staged_blocks). The scan's own fp64
-// chain (gain_rows: W, K, y, the eager robot-strip and diagonal-block downdates, the corrections
-// of later lines) keeps K·S·Kᵀ; only the stored operands take this form.
-__device__ __forceinline__ void sym_factor_S(const double S[4], float F[3])
-{
-    const float a = (float)S[0], b = 0.5f * ((float)S[1] + (float)S[2]);
-    const float c = (float)S[3];
-    // v_rsq_f32 (1 ulp): F need not be correctly rounded, only the same on every thread
-    F[0] = F[1] = F[2] = 0.f;
-    if (a > 0.f) {
-        const float ra = __builtin_amdgcn_rsqf(a);
-        F[0] = a * ra;
-        F[1] = b * ra;
-        const float dd = c - F[1] * F[1];
-        F[2] = dd > 0.f ? dd * __builtin_amdgcn_rsqf(dd) : 0.f;
-    } else {
-        F[2] = c > 0.f ? c * __builtin_amdgcn_rsqf(c) : 0.f;
-    }
-}
-
-__device__ __forceinline__ void sym_factor(const double* pk, float F[3])
-{
-    const double S[4] = {pk[MB_S], pk[MB_S + 1], pk[MB_S + 2], pk[MB_S + 3]};
-    sym_factor_S(S, F);
-}
-
-// The uniform gain package of a match from the matching landmark's state: S, S⁻¹, v, H row 1
-// and the robot rows of K = W·S⁻¹ and U = K·S (Robot.cpp:522-602 for rows 0..2).
-__device__ __forceinline__ void build_package(const Cand& c, const double R33[9], double2 rr0,
-                                              double2 rr1, double2 rr2, double* pk)
-{
-    const double RL0[3] = {rr0.x, rr1.x, rr2.x};
-    const double RL1[3] = {rr0.y, rr1.y, rr2.y};
-    pk[MB_S + 0] = c.S[0]; pk[MB_S + 1] = c.S[1];
-    pk[MB_S + 2] = c.S[2]; pk[MB_S + 3] = c.S[3];
-    pk[MB_SI + 0] = c.Si[0]; pk[MB_SI + 1] = c.Si[1];
-    pk[MB_SI + 2] = c.Si[2]; pk[MB_SI + 3] = c.Si[3];
-    pk[MB_V + 0] = c.v[0]; pk[MB_V + 1] = c.v[1];
-    pk[MB_H + 0] = c.h10; pk[MB_H + 1] = c.h11; pk[MB_H + 2] = c.h1l;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        // W = P·Hᵀ (Robot.cpp:522), K = W·S⁻¹ (:526), U = K·S (:560)
-        const double w0 = -R33[a * 3 + 2] + RL0[a];
-        const double w1 = c.h10 * R33[a * 3 + 0] + c.h11 * R33[a * 3 + 1] + c.h1l * RL0[a] + RL1[a];
-        const double k0 = w0 * c.Si[0] + w1 * c.Si[2];
-        const double k1 = w0 * c.Si[1] + w1 * c.Si[3];
-        pk[MB_KR + 2 * a] = k0;
-        pk[MB_KR + 2 * a + 1] = k1;
-        pk[MB_UR + 2 * a] = k0 * c.S[0] + k1 * c.S[2];
-        pk[MB_UR + 2 * a + 1] = k0 * c.S[1] + k1 * c.S[3];
-    }
-}
-
-// The two rows of one landmark for a match: its block of column jstar with the earlier matches
-// of the scan applied (Robot.cpp:560-568, in order), W = P·Hᵀ, K = W·S⁻¹, U = K·S, y += K·v
-// (Robot.cpp:522-589), and the eager downdate of its robot-strip columns and diagonal block.
-// `uq_of(q)` / `vq_of(q)` return the landmark's U rows and jstar's V rows of the scan's match q.
-// MAXQ > 0: at most MAXQ earlier matches (the speculative path). (Applying all MAXQ rows
-// branch-free on zeroed rows measured slower: DESIGN.md §10.)
-// One earlier match q's correction of a landmark's block of a later match's column (Robot.cpp:560-568
-// in order): blk −= U_q(own rows)·V_q(column rows)ᵀ, four independent fused chains. Every path that
-// corrects a block (gain_rows, all at once; the speculative landmark waves, one match at a time)
-// runs this sequence per element, so they agree bit for bit.
-__device__ __forceinline__ void correct_block(double blk[4], const double4& uq, const double4& vh)
-{
-    blk[0] = fma(-uq.x, vh.x, blk[0]);
-    blk[1] = fma(-uq.x, vh.z, blk[1]);
-    blk[2] = fma(-uq.z, vh.x, blk[2]);
-    blk[3] = fma(-uq.z, vh.z, blk[3]);
-    blk[0] = fma(-uq.y, vh.y, blk[0]);
-    blk[1] = fma(-uq.y, vh.w, blk[1]);
-    blk[2] = fma(-uq.w, vh.y, blk[2]);
-    blk[3] = fma(-uq.w, vh.w, blk[3]);
-}
-
-// The package words the landmark rows of a match read (Robot.cpp:522-589): S, S⁻¹, v, H row 1 and
-// the robot rows of U = K·S
-struct PkCore {
-    double S[4], Si[4], v[2], h[3], Ur[6];
-};
-__device__ __forceinline__ void gain_core(const PkCore& P, const double blk[4], double2& rr0, double2& rr1,
-                                          double2& rr2, double2& yb, double Dj[4], double kk[4], double uu[4]);
-
-template <int MAXQ, typename UQ, typename VQ>
-__device__ __forceinline__ void gain_rows(const double* pk, int t, UQ uq_of, VQ vq_of, double blk[4],
-                                          double2& rr0, double2& rr1, double2& rr2, double2& yb,
-                                          double Dj[4], double kk[4], double uu[4])
-{
-    // earlier matches of this scan, in order: four independent fused chains (one per entry), the
-    // rows of match q + 1 loaded before match q's products (LDS latency off the chain). t is the
-    // scan's match count, the same on every lane: a scalar loop
-    auto correct = [&](const double4& uq, const double4& vh) __attribute__((always_inline)) {
-        correct_block(blk, uq, vh);
-    };
-    // matches in pairs (both pairs' rows loaded together: one LDS round trip per two matches),
-    // then the odd one; the products in q order either way
-    const int tu = __builtin_amdgcn_readfirstlane(MAXQ > 0 ? min(t, MAXQ) : t);
-    int q = 0;
-#pragma unroll 1
-    for (; q + 1 < tu; q += 2) {
-        const double4 ua = uq_of(q), va = vq_of(q);
-        const double4 ub = uq_of(q + 1), vb = vq_of(q + 1);
-        correct(ua, va);
-        correct(ub, vb);
-    }
-    if (q < tu) correct(uq_of(q), vq_of(q));
-    PkCore P;
-#pragma unroll
-    for (int a = 0; a < 4; a++) {
-        P.S[a] = pk[MB_S + a];
-        P.Si[a] = pk[MB_SI + a];
-    }
-    P.v[0] = pk[MB_V];
-    P.v[1] = pk[MB_V + 1];
-    P.h[0] = pk[MB_H];
-    P.h[1] = pk[MB_H + 1];
-    P.h[2] = pk[MB_H + 2];
-#pragma unroll
-    for (int a = 0; a < 6; a++) P.Ur[a] = pk[MB_UR + a];
-    gain_core(P, blk, rr0, rr1, rr2, yb, Dj, kk, uu);
-}
-
-// The gain rows from the corrected block (gain_rows without the earlier matches' corrections),
-// the package's words in registers: every path computes them with this one expression set
-__device__ __forceinline__ void gain_core(const PkCore& P, const double blk[4], double2& rr0, double2& rr1,
-                                          double2& rr2, double2& yb, double Dj[4], double kk[4], double uu[4])
-{
-    const double S0 = P.S[0], S1 = P.S[1], S2 = P.S[2], S3 = P.S[3];
-    const double Si0 = P.Si[0], Si1 = P.Si[1], Si2 = P.Si[2], Si3 = P.Si[3];
-    const double v0 = P.v[0], v1 = P.v[1];
-    const double h10 = P.h[0], h11 = P.h[1], h1l = P.h[2];
-#pragma unroll
-    for (int pp = 0; pp < 2; pp++) {
-        const double pb0 = pp ? rr0.y : rr0.x;
-        const double pb1 = pp ? rr1.y : rr1.x;
-        const double pb2 = pp ? rr2.y : rr2.x;
-        const double pba = blk[pp * 2 + 0], pbb = blk[pp * 2 + 1];
-        const double w0 = -pb2 + pba;
-        const double w1 = h10 * pb0 + h11 * pb1 + h1l * pba + pbb;
-        const double k0 = w0 * Si0 + w1 * Si2;
-        const double k1 = w0 * Si1 + w1 * Si3;
-        kk[2 * pp] = k0;
-        kk[2 * pp + 1] = k1;
-        uu[2 * pp] = k0 * S0 + k1 * S2;
-        uu[2 * pp + 1] = k0 * S1 + k1 * S3;
-        const double dyv = k0 * v0 + k1 * v1;   // y += K·v (Robot.cpp:585-589)
-        if (pp) yb.y += dyv; else yb.x += dyv;
-    }
-    const double* Ur = P.Ur;
-    // eager downdate of the robot-strip columns and the diagonal block (Robot.cpp:568)
-    rr0.x -= Ur[0] * kk[0] + Ur[1] * kk[1];
-    rr0.y -= Ur[0] * kk[2] + Ur[1] * kk[3];
-    rr1.x -= Ur[2] * kk[0] + Ur[3] * kk[1];
-    rr1.y -= Ur[2] * kk[2] + Ur[3] * kk[3];
-    rr2.x -= Ur[4] * kk[0] + Ur[5] * kk[1];
-    rr2.y -= Ur[4] * kk[2] + Ur[5] * kk[3];
-    Dj[0] -= uu[0] * kk[0] + uu[1] * kk[1];
-    Dj[1] -= uu[0] * kk[2] + uu[1] * kk[3];
-    Dj[2] -= uu[2] * kk[0] + uu[3] * kk[1];
-    Dj[3] -= uu[2] * kk[2] + uu[3] * kk[3];
-}
-
-// uniform: robot 3×3 block and x_pre = y[0..2] after a match (Robot.cpp:568, 579-602)
-__device__ __forceinline__ void robot_update(double R33[9], double xp[3], const double* pk)
-{
-    double Kr[6], Ur[6];
-#pragma unroll
-    for (int q = 0; q < 6; q++) {
-        Kr[q] = pk[MB_KR + q];
-        Ur[q] = pk[MB_UR + q];
-    }
-    const double v0 = pk[MB_V], v1 = pk[MB_V + 1];
-    double yn[3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        yn[a] = xp[a] + (Kr[2 * a] * v0 + Kr[2 * a + 1] * v1);
-#pragma unroll
-        for (int cc = 0; cc < 3; cc++)
-            R33[a * 3 + cc] -= Ur[2 * a] * Kr[2 * cc] + Ur[2 * a + 1] * Kr[2 * cc + 1];
-    }
-    xp[0] = yn[0];
-    xp[1] = yn[1];
-    xp[2] = normalize_radian(yn[2]);   // Robot.cpp:596
 }
 
 // Cheap guess of the exact gate (fp32 sine/cosine, no error bounds). It only steers the
@@ -2929,1015 +2537,6 @@ __global__ __launch_bounds__(NT + 64) void scan_kernel(ScanParams p)
         for (int k = 0; k < EKF_NSTAMP; k++) dbg[k] += sh_stamp[k];
         dbg[8] += t_last - t_first;
         dbg[9] += 1;
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// One instance with its landmark block partitioned over ranks (ShardParams): the
-// scan kernel's sequential association path phase by phase over every landmark, one thread per
-// landmark, every expression the scan kernel's (the same inline functions in this contract(on)
-// region), so that a sharded run is bit-identical to a single-context one. Between phases the
-// caller sums the [N][4] exchange buffer over the ranks (each fills the blocks its tiles hold).
-// Predict (Robot.cpp:130-286) as the scan kernel's init_state: F3, x_pre and the 3×3 block
-__device__ __forceinline__ void shard_predict(const double pose[3], const double enc[3], double enc_noise,
-                                              double F3[9], double R33[9], double xp[3])
-{
-    const double x0 = pose[0], y0 = pose[1], t0 = pose[2];
-    const double u2 = t0 - enc[2];
-    const double dx = x0 - enc[0], dy = y0 - enc[1];
-    const double u0 = sqrt(dx * dx + dy * dy);
-    const double c = u2 / 2.0 + t0;
-    double sc, cc;
-    sincos(c, &sc, &cc);
-    F3[2] = -u0 * sc;
-    F3[5] = u0 * cc;
-    xp[0] = x0 + u0 * cc;
-    xp[1] = y0 + u0 * sc;
-    xp[2] = t0 + u2;
-    const double Fu3[9] = {cc, 0, -u0 * sc / 2.0, sc, 1, u0 * cc / 2.0, 0, 0, 1};
-    const double qs = (-1.0 / (1 + fabs(u0)) + 1);
-    const double Q[9] = {enc_noise * qs, 0, 0, 0, 2 * enc_noise * qs, 0, 0, 0, enc_noise * qs};
-    double FP[9], FuQ[9];
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) {
-            double s = 0.0, t = 0.0;
-            for (int k = 0; k < 3; k++) {
-                s += F3[a * 3 + k] * R33[k * 3 + b];
-                t += Fu3[a * 3 + k] * Q[k * 3 + b];
-            }
-            FP[a * 3 + b] = s;
-            FuQ[a * 3 + b] = t;
-        }
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) {
-            double s = 0.0, t = 0.0;
-            for (int k = 0; k < 3; k++) {
-                s += FP[a * 3 + k] * F3[b * 3 + k];
-                t += FuQ[a * 3 + k] * Fu3[b * 3 + k];
-            }
-            R33[a * 3 + b] = s + t;
-        }
-}
-
-// One phase of the partitioned instance's scan for landmark j (every rank runs every landmark):
-// shard_kernel runs one phase over a grid, shard_run_kernel the per-line phases of the
-// speculative path in one workgroup (its ctl, robot and package words in LDS).
-template <typename T>
-__device__ __forceinline__ void shard_step(const ShardParams& p, const int phase, const int line, const int j,
-                                           const PllView<T>& pv)
-{
-    using C = typename Stor<T>::C;
-    constexpr double ETA = gate_eta<T>();
-    const Dims d = p.d;
-    const int n = d.n;
-    const bool own = j < d.N;
-    int* ctl = p.ctl;
-    // block (j, w) of the landmark block is this rank's if the tile that stores it is
-    auto local_blk = [&](int ja, int wb) {
-        const int ba = (2 * ja) >> 5, bb = (2 * wb) >> 5;
-        const long long t = tile_index(ba < bb ? ba : bb, ba < bb ? bb : ba, d.nb);
-        return t >= p.t0 && t < p.t1;
-    };
-    const bool sym = p.r_mode != 1 && sizeof(C) == 4;
-    const int b0 = 3 + 2 * j;
-    double* rc = p.rec + (size_t)j * SH_REC;
-    double R33[9], xp[3];
-    if (phase != SH_BEGIN) {
-#pragma unroll
-        for (int a = 0; a < 9; a++) R33[a] = p.rob[a];
-        xp[0] = p.rob[9]; xp[1] = p.rob[10]; xp[2] = p.rob[11];
-    }
-    if (phase == SH_ROBOT) {
-        // after line `line` (one thread): the robot block and x_pre after its match (Robot.cpp:560-602),
-        // the match list, and the winner word reset for the next line's gate
-        if (j == 0) {
-            const int jstar = ctl[SC_WIN];
-            if (jstar != 0x7fffffff) {
-                robot_update(R33, xp, p.pkg);
-#pragma unroll
-                for (int a = 0; a < 9; a++) p.rob[a] = R33[a];
-                p.rob[9] = xp[0]; p.rob[10] = xp[1]; p.rob[11] = xp[2];
-                ctl[SC_MATCH + line] = jstar;
-                ctl[SC_M] += 1;
-            } else {
-                ctl[SC_MATCH + line] = -1;
-                ctl[SC_EXTRA + ctl[SC_NEXTRA]] = line;
-                ctl[SC_NEXTRA] += 1;
-            }
-            ctl[SC_WIN] = 0x7fffffff;
-        }
-        return;
-    }
-
-    if (phase == SH_BEGIN) {
-        // the committed robot block and pose, predicted (every thread the same), every landmark's
-        // strip columns predicted (Robot.cpp:242) and scan-start angle; the rank's diagonal blocks
-        // with the pending steps applied into the exchange buffer (zero where another rank's)
-        const int s = p.saved[0];
-#pragma unroll
-        for (int a = 0; a < 9; a++) R33[a] = p.Rs[(a / 3) * n + (a % 3)];
-        double F3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        shard_predict(p.pose, p.enc_v, p.enc_noise, F3, R33, xp);
-        if (j == 0) {
-            // the scan's inputs, handed over as kernel arguments (no host staging copy), for the
-            // later phases
-            double* enc = const_cast<double*>(p.enc);
-            enc[0] = p.enc_v[0]; enc[1] = p.enc_v[1]; enc[2] = p.enc_v[2];
-            ekf_line* lines = const_cast<ekf_line*>(p.lines);
-            for (int i = 0; i < d.max_lines; i++) lines[i] = p.lines_v[i];
-#pragma unroll
-            for (int a = 0; a < 9; a++) p.rob[a] = R33[a];
-            p.rob[9] = xp[0]; p.rob[10] = xp[1]; p.rob[11] = xp[2];
-            ctl[SC_WIN] = 0x7fffffff;
-            ctl[SC_STATUS] = 0;
-            ctl[SC_M] = 0;
-            ctl[SC_NEXTRA] = 0;
-            ctl[SC_S] = s;
-            ctl[SC_NEXT] = 0;
-            for (int i = 0; i < EKF_MAX_LINES; i++) ctl[SC_GUESS + i] = 0x7fffffff;
-        }
-        if (!own) return;
-        double2 rr0 = *reinterpret_cast<const double2*>(p.Rs + b0);
-        double2 rr1 = *reinterpret_cast<const double2*>(p.Rs + n + b0);
-        double2 rr2 = *reinterpret_cast<const double2*>(p.Rs + 2 * n + b0);
-        const double2 yb = *reinterpret_cast<const double2*>(p.y + b0);
-        predict_cols(F3, rr0, rr1, rr2);
-        double Dj[4] = {0, 0, 0, 0};
-        if (j < s && local_blk(j, j)) pll_block(pv, 2 * j, 2 * j, Dj);
-        double s0j, c0j;
-        sincos(yb.x, &s0j, &c0j);
-        float s0f, c0f;
-        __sincosf((float)yb.x, &s0f, &c0f);
-        const double v[SH_REC] = {rr0.x, rr0.y, rr1.x, rr1.y, rr2.x, rr2.y, yb.x, yb.y, 0, 0, 0, 0,
-                                  yb.x, s0j, c0j, (double)s0f, (double)c0f, 0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < SH_REC; k++) rc[k] = v[k];
-        *reinterpret_cast<double4*>(p.col + 4 * (size_t)j) = make_double4(Dj[0], Dj[1], Dj[2], Dj[3]);
-        p.flags[j] = 0;
-        return;
-    }
-    if (!own) return;
-    const bool fused_diag = phase == SH_GUESS && p.diag_first;
-    double4 dj = make_double4(0, 0, 0, 0);
-    if (phase == SH_DIAG || fused_diag) {
-        // the summed diagonal blocks (every rank contributed its own); the guesses may follow in
-        // the same launch, which reads them from the sum (its grid row 0 stores them)
-        dj = *reinterpret_cast<const double4*>(p.col + 4 * (size_t)j);
-        if (phase == SH_DIAG || line == 0) {
-            rc[8] = dj.x; rc[9] = dj.y; rc[10] = dj.z; rc[11] = dj.w;
-        }
-        if (phase == SH_DIAG) return;
-    }
-    const int s = ctl[SC_S];
-    double2 rr0 = make_double2(rc[0], rc[1]), rr1 = make_double2(rc[2], rc[3]), rr2 = make_double2(rc[4], rc[5]);
-    double2 yb = make_double2(rc[6], rc[7]);
-    double Dj[4] = {rc[8], rc[9], rc[10], rc[11]};
-    if (fused_diag) {
-        Dj[0] = dj.x; Dj[1] = dj.y; Dj[2] = dj.z; Dj[3] = dj.w;
-    }
-    const double ma0 = rc[12], s0j = rc[13], c0j = rc[14];
-    const double s0f = rc[15], c0f = rc[16];
-    int fl = p.flags[j];
-    ekf_line ln = p.lines[line < 0 ? 0 : line];
-    double Rm[4];
-    line_R(ln, line, p.r_mode, Rm);
-
-    // the gate of one landmark exactly as the sequential path (Robot.cpp:313-498)
-    auto gate_of = [&](Cand& c, bool& pass, bool& sing, bool& amb) {
-        Block5 b5;
-        fill_block5(b5, R33, rr0, rr1, rr2, Dj);
-        double sn, cs;
-        pass = sing = amb = false;
-        if (!quick_reject(b5, yb.x, yb.y, ma0, s0f, c0f, xp, ln.alpha, ln.r, Rm, p.gate, ETA) &&
-            (sincos_near(yb.x, ma0, s0j, c0j, sn, cs),
-             !certified_reject(b5, yb.x, yb.y, sn, cs, xp, ln.alpha, ln.r, Rm, p.gate, ETA))) {
-            eval_candidate(b5, yb.x, yb.y, sn, cs, xp, ln.alpha, ln.r, Rm, p.gate, ETA, c);
-            sing = c.singular;
-            amb = c.amb;
-            pass = c.pass;
-        }
-    };
-
-    if (phase == SH_GUESS) {
-        // every line's first passing landmark at the scan's start (no line applied yet): the
-        // speculative path fetches these columns in one exchange; shard_run_kernel checks each
-        // line's real winner against its guess
-        // (one line per grid row)
-        if (!(j < s)) return;
-        Cand c;
-        bool pass, sing, amb;
-        gate_of(c, pass, sing, amb);
-        if (pass) atomicMin(ctl + SC_GUESS + line, j);
-        return;
-    }
-    if (phase == SH_SPEC_COLS) {
-        // the rank's blocks of the guessed column of line `line` (one line per grid row), pending
-        // steps applied (SH_COLUMN's blocks)
-        {
-            const int i = line;
-            const int w = ctl[SC_GUESS + i];
-            double blk[4] = {0, 0, 0, 0};
-            if (w != 0x7fffffff && local_blk(j, w)) pll_block(pv, 2 * j, 2 * w, blk);
-            *reinterpret_cast<double4*>(p.cols + 4 * ((size_t)i * d.N + j)) = make_double4(blk[0], blk[1], blk[2], blk[3]);
-        }
-        return;
-    }
-    if (phase == SH_PACKAGE) {   // (the winner's thread) SH_COLUMN's package, without the column
-        Cand c;
-        bool pass, sing, amb;
-        gate_of(c, pass, sing, amb);
-        build_package(c, R33, rr0, rr1, rr2, p.pkg);
-        const int m = ctl[SC_M];
-        for (int q = 0; q < m; q++) {
-            const double* h = p.hist + ((size_t)j * d.max_lines + q) * 8 + 4;
-            p.pkg[MB_VH + 4 * q + 0] = h[0];
-            p.pkg[MB_VH + 4 * q + 1] = h[1];
-            p.pkg[MB_VH + 4 * q + 2] = h[2];
-            p.pkg[MB_VH + 4 * q + 3] = h[3];
-        }
-        return;
-    }
-
-    if (phase == SH_GATE) {
-        // the first passing unmatched landmark of the line: every rank finds the same one
-        if (!(j < s) || (fl & 1)) {
-            p.flags[j] = fl & 1;
-            return;
-        }
-        Cand c;
-        bool pass, sing, amb;
-        gate_of(c, pass, sing, amb);
-        p.flags[j] = (fl & 1) | (sing ? 2 : 0) | (amb ? 4 : 0);
-        if (pass) {
-            atomicMin(ctl + SC_WIN, j);
-            if (p.pkg_slot) {   // (shard_run_kernel) SH_PACKAGE's package from this evaluation
-                double* slot = p.pkg_slot + (size_t)threadIdx.x * SH_PKG_WORDS;
-                build_package(c, R33, rr0, rr1, rr2, slot);
-                const int m = ctl[SC_M];
-                for (int q = 0; q < m; q++) {
-                    const double* h = p.hist + ((size_t)j * d.max_lines + q) * 8 + 4;
-                    slot[MB_VH + 4 * q + 0] = h[0];
-                    slot[MB_VH + 4 * q + 1] = h[1];
-                    slot[MB_VH + 4 * q + 2] = h[2];
-                    slot[MB_VH + 4 * q + 3] = h[3];
-                }
-            }
-        }
-        return;
-    }
-
-    if (phase == SH_COLUMN) {
-        // the winner's gain package (its thread) and the rank's blocks of its column, with the
-        // pending steps applied, into the exchange buffer (zero where another rank's)
-        const int jstar = ctl[SC_WIN];
-        double blk[4] = {0, 0, 0, 0};
-        if (jstar != 0x7fffffff) {
-            if (local_blk(j, jstar)) pll_block(pv, 2 * j, 2 * jstar, blk);
-            if (j == jstar) {
-                Cand c;
-                bool pass, sing, amb;
-                gate_of(c, pass, sing, amb);
-                build_package(c, R33, rr0, rr1, rr2, p.pkg);
-                const int m = ctl[SC_M];
-                for (int q = 0; q < m; q++) {   // the winner's V rows of the earlier matches (Robot.cpp:560-568)
-                    const double* h = p.hist + ((size_t)j * d.max_lines + q) * 8 + 4;
-                    p.pkg[MB_VH + 4 * q + 0] = h[0];
-                    p.pkg[MB_VH + 4 * q + 1] = h[1];
-                    p.pkg[MB_VH + 4 * q + 2] = h[2];
-                    p.pkg[MB_VH + 4 * q + 3] = h[3];
-                }
-            }
-        }
-        *reinterpret_cast<double4*>(p.col + 4 * (size_t)j) = make_double4(blk[0], blk[1], blk[2], blk[3]);
-        return;
-    }
-
-    if (phase == SH_APPLY) {
-        const int jstar = ctl[SC_WIN];
-        // GSL_EDOM counts only for the candidates the reference evaluates (up to the winner)
-        int st = (fl & 2) && j <= jstar ? (int)EKF_ST_SINGULAR : 0;
-        if ((fl & 4) && j <= jstar) st |= EKF_ST_PRECISION_BIT;   // (gate_eta)
-        if (p.r_mode == 1 && (line == 1 || line == 2)) st |= EKF_ST_NSYM;
-        if (st) atomicOr(ctl + SC_STATUS, st);
-        if (jstar == 0x7fffffff) return;
-        const double4 cb = *reinterpret_cast<const double4*>(p.col + 4 * (size_t)j);   // summed over ranks
-        double blk[4] = {cb.x, cb.y, cb.z, cb.w};
-        const double* pk = p.pkg;
-        const int m = ctl[SC_M];
-        double kk[4], uu[4];
-        gain_rows<0>(pk, m,
-                     [&](int q) {
-                         const double* h = p.hist + ((size_t)j * d.max_lines + q) * 8;
-                         return make_double4(h[0], h[1], h[2], h[3]);
-                     },
-                     [&](int q) {
-                         const double* vh = pk + MB_VH + 4 * q;
-                         return make_double4(vh[0], vh[1], vh[2], vh[3]);
-                     },
-                     blk, rr0, rr1, rr2, yb, Dj, kk, uu);
-        float F[3] = {0.f, 0.f, 0.f};
-        if (sym) sym_factor(pk, F);
-        // store_rows (the scan kernel's non-staged form: the same values)
-        double* h = p.hist + ((size_t)j * d.max_lines + m) * 8;
-        h[0] = uu[0]; h[1] = uu[1]; h[2] = uu[2]; h[3] = uu[3];
-        h[4] = kk[0]; h[5] = kk[1]; h[6] = kk[2]; h[7] = kk[3];
-        C* Uop = reinterpret_cast<C*>(p.cur.Uop);
-        C* Vop = reinterpret_cast<C*>(p.cur.Vop);
-#pragma unroll
-        for (int pp = 0; pp < 2; pp++) {
-            const int lr = 2 * j + pp;
-            if constexpr (sizeof(C) == 4) {
-                double o0 = uu[2 * pp], o1 = uu[2 * pp + 1], v0 = kk[2 * pp], v1 = kk[2 * pp + 1];
-                if (sym) {
-                    v0 = kk[2 * pp] * (double)F[0] + kk[2 * pp + 1] * (double)F[1];
-                    v1 = kk[2 * pp + 1] * (double)F[2];
-                    o0 = (double)(float)v0;
-                    o1 = (double)(float)v1;
-                }
-                Uop[op_index_f32(lr, 2 * m, d.kmax)] = to_domain<T>(-o0, pv.ex);
-                Uop[op_index_f32(lr, 2 * m + 1, d.kmax)] = to_domain<T>(-o1, pv.ex);
-                Vop[op_index_f32(lr, 2 * m, d.kmax)] = (C)v0;
-                Vop[op_index_f32(lr, 2 * m + 1, d.kmax)] = (C)v1;
-            } else {
-                Uop[op_index_f64(lr, 2 * m, d.kmax)] = (C)(-uu[2 * pp]);
-                Uop[op_index_f64(lr, 2 * m + 1, d.kmax)] = (C)(-uu[2 * pp + 1]);
-                Vop[op_index_f64(lr, 2 * m, d.kmax)] = (C)kk[2 * pp];
-                Vop[op_index_f64(lr, 2 * m + 1, d.kmax)] = (C)kk[2 * pp + 1];
-            }
-        }
-        if (j == jstar) fl |= 1;
-        p.flags[j] = fl & 1;
-        const double v[12] = {rr0.x, rr0.y, rr1.x, rr1.y, rr2.x, rr2.y, yb.x, yb.y, Dj[0], Dj[1], Dj[2], Dj[3]};
-#pragma unroll
-        for (int k = 0; k < 12; k++) rc[k] = v[k];
-        return;
-    }
-
-    // SH_END: augmentation (Robot.cpp:776-866) as the scan kernel's commit: the new landmarks' rows
-    // to the step's patch buffer (every rank all of them: its flush takes the columns of its tiles),
-    // the new landmarks' strip columns and mean, the 2×2 diagonal blocks; the capacity reset
-    // (Robot.cpp:893-904)
-    if (p.end_gate) {
-        // (ekf_shard_localize) launched behind the speculative run before the host has read the
-        // agreement: a run that stopped short or failed on some rank leaves everything untouched
-        const double a0 = p.end_gate[0], a1 = p.end_gate[1];
-        if (j == 0) {
-            p.end_gate_host[0] = a0;
-            p.end_gate_host[1] = a1;
-            __threadfence_system();
-        }
-        if (a0 > 0.0 || a1 != (double)p.L) return;
-    }
-    const int m = ctl[SC_M], nextra = ctl[SC_NEXTRA];
-    double pose[3] = {xp[0], xp[1], xp[2]};
-    if (p.L == 0 || m == 0) pose[2] = normalize_radian(xp[2]);
-    const int N = d.N, M = d.M;
-    const int nadd = min(nextra, N - s);
-    const int reset = (s + nadd > N - p.reset_margin) ? 1 : 0;
-    double* patch = p.cur.patch;
-    double* pdiag = p.cur.patch_diag;
-    if (!reset) {
-        for (int q = 0; q < nadd; q++) {
-            const ekf_line lq = p.lines[ctl[SC_EXTRA + q]];
-            const int sq = s + q;
-            double alfa = lq.alpha;
-            const double r = lq.r + (pose[0] * cos(alfa) + pose[1] * sin(alfa));
-            alfa += pose[2];
-            double sa, ca;
-            sincos(alfa, &sa, &ca);
-            if (j < sq) {
-                double* prow = patch + (size_t)(q * 2) * M;
-                *reinterpret_cast<double2*>(prow + 2 * j) = rr2;
-                double2 gx;
-                gx.x = ca * rr0.x + sa * rr1.x;
-                gx.y = ca * rr0.y + sa * rr1.y;
-                *reinterpret_cast<double2*>(prow + M + 2 * j) = gx;
-            }
-            if (j == sq) {
-                rr0 = make_double2(R33[6], ca * R33[0] + sa * R33[3]);
-                rr1 = make_double2(R33[7], ca * R33[1] + sa * R33[4]);
-                rr2 = make_double2(R33[8], ca * R33[2] + sa * R33[5]);
-                yb = make_double2(normalize_radian(alfa), r);
-            }
-            if (j == 0) {
-                const double Gx[6] = {0, 0, 1, ca, sa, 0};
-                const double Gl[4] = {1.0, 0, xp[1] * ca - xp[0] * sa, 1};
-                double GP[6], GlR[4];
-                for (int a = 0; a < 2; a++)
-                    for (int b = 0; b < 3; b++) {
-                        double acc = 0.0;
-                        for (int k = 0; k < 3; k++) acc += Gx[a * 3 + k] * R33[k * 3 + b];
-                        GP[a * 3 + b] = acc;
-                    }
-                for (int a = 0; a < 2; a++)
-                    for (int b = 0; b < 2; b++)
-                        GlR[a * 2 + b] = Gl[a * 2 + 0] * lq.R[0 * 2 + b] + Gl[a * 2 + 1] * lq.R[1 * 2 + b];
-                for (int a = 0; a < 2; a++)
-                    for (int b = 0; b < 2; b++) {
-                        double gsum = 0.0;
-                        for (int k = 0; k < 3; k++) gsum += GP[a * 3 + k] * Gx[b * 3 + k];
-                        const double hh = GlR[a * 2 + 0] * Gl[b * 2 + 0] + GlR[a * 2 + 1] * Gl[b * 2 + 1];
-                        pdiag[q * 4 + a * 2 + b] = gsum + hh;
-                    }
-            }
-        }
-    }
-    if (reset) rr0 = rr1 = rr2 = yb = make_double2(0.0, 0.0);
-    // the strip columns and mean, the operand padding past the matches
-    *reinterpret_cast<double2*>(p.Rs + b0) = rr0;
-    *reinterpret_cast<double2*>(p.Rs + n + b0) = rr1;
-    *reinterpret_cast<double2*>(p.Rs + 2 * n + b0) = rr2;
-    *reinterpret_cast<double2*>(p.y + b0) = yb;
-    C* Uop = reinterpret_cast<C*>(p.cur.Uop);
-    C* Vop = reinterpret_cast<C*>(p.cur.Vop);
-    for (int k = 2 * m; k < d.kmax; k++)
-#pragma unroll
-        for (int pp = 0; pp < 2; pp++) {
-            if constexpr (sizeof(C) == 4) {
-                Uop[op_index_f32(2 * j + pp, k, d.kmax)] = (C)(-0.0f);
-                Vop[op_index_f32(2 * j + pp, k, d.kmax)] = (C)0.0f;
-            } else {
-                Uop[op_index_f64(2 * j + pp, k, d.kmax)] = (C)(-0.0);
-                Vop[op_index_f64(2 * j + pp, k, d.kmax)] = (C)0.0;
-            }
-        }
-    if (j == 0) {
-        // commit (Robot.cpp:702-716)
-        for (int a = 0; a < 9; a++) p.Rs[(a / 3) * n + (a % 3)] = R33[a];
-        p.y[0] = xp[0]; p.y[1] = xp[1]; p.y[2] = xp[2];
-        p.pose[0] = pose[0]; p.pose[1] = pose[1]; p.pose[2] = pose[2];
-        int* res = p.cur.res;
-        res[RES_NLINES] = p.L;
-        res[RES_SAVED_IN] = s;
-        res[RES_DBG] = 16;
-        res[RES_STATUS] = ((nextra > nadd) ? EKF_ST_CAP : 0) | ctl[SC_STATUS];
-        res[RES_M] = m;
-        res[RES_NEXTRA] = nextra;
-        res[RES_SAVED] = reset ? 0 : s + nadd;
-        res[RES_RESET] = reset;
-        res[RES_NADD] = reset ? 0 : nadd;
-        res[RES_KSTEPS] = (sizeof(C) == 4) ? m : (m + 1) / 2;
-        res[RES_ROLLBACK] = 0;
-        for (int i = 0; i < p.L; i++) res[RES_MATCH + i] = ctl[SC_MATCH + i];
-        for (int q = 0; q < nextra; q++) res[RES_EXTRA + q] = ctl[SC_EXTRA + q];
-        p.saved[0] = reset ? 0 : s + nadd;
-        if (p.res_host) {
-            // the words ekf_result takes, for the host to read after this kernel without a copy
-            // (each store crosses to host memory: only these, not the whole record)
-            int* rh = p.res_host;
-            rh[RES_NLINES] = res[RES_NLINES];
-            rh[RES_STATUS] = res[RES_STATUS];
-            rh[RES_M] = res[RES_M];
-            rh[RES_NEXTRA] = res[RES_NEXTRA];
-            rh[RES_SAVED] = res[RES_SAVED];
-            rh[RES_RESET] = res[RES_RESET];
-            for (int i = 0; i < p.L; i++) rh[RES_MATCH + i] = res[RES_MATCH + i];
-            p.pose_host[0] = pose[0]; p.pose_host[1] = pose[1]; p.pose_host[2] = pose[2];
-            __threadfence_system();
-        }
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(SH_THREADS) void shard_kernel(ShardParams p)
-{
-    __shared__ int4 sh_ctl[PMAX];
-    for (int q = threadIdx.x; q < p.npend; q += blockDim.x) {
-        const int* r = p.pend[q].res;
-        sh_ctl[q] = make_int4(r[RES_RESET], r[RES_KSTEPS], r[RES_NADD], r[RES_SAVED_IN]);
-    }
-    __syncthreads();
-    const Dims d = p.d;
-    PllView<T> pv;
-    pv.X = reinterpret_cast<const T*>(p.Pread);
-    pv.nb = d.nb;
-    pv.kmax = d.kmax;
-    pv.M = d.M;
-    pv.max_lines = d.max_lines;
-    pv.e = 0;
-    pv.ex = storage_exp<T>(p.pexp, 0);
-    pv.opstride = (size_t)d.nb * 64 * (d.kmax / 2);
-    pv.usym = 0;   // (the partitioned instance stores its U rows)
-    pv.us = 1.0f;
-    pv.npend = p.npend;
-    pv.pend = p.pend;
-    pv.ctl = sh_ctl;
-    pv.rnd = 1;
-    // (SH_GUESS, SH_SPEC_COLS: grid row y = the line)
-    shard_step<T>(p, p.phase, (p.phase == SH_SPEC_COLS || p.phase == SH_GUESS) ? (int)blockIdx.y : p.line,
-                  (int)(blockIdx.x * blockDim.x + threadIdx.x), pv);
-}
-
-// The speculative path's lines (ekf_shard_run): G cooperating workgroups run lines 0 .. L − 1 of
-// the sequential association exactly as the per-line phases do (gate of every landmark, the
-// winner's package, gain rows, robot update), taking each winner's column from the exchanged
-// guessed columns (p.cols) instead of a per-line exchange between ranks. Landmark j belongs to
-// thread j mod SHR_THREADS of workgroup ⌊j / SHR_THREADS⌋ mod G for the whole run (its records,
-// U/V history and flags are only ever touched by that thread). Every workgroup holds its own
-// copy of the control words, the robot block and the package in LDS and updates them itself
-// (SH_ROBOT: the same bits in every workgroup). Per line one exchange among the workgroups, the
-// scan kernel's sequential-path mailbox: each publishes its first passing landmark and, when it has
-// one, that landmark's package (built before the exchange), then polls every workgroup's tag; all
-// take the smallest landmark and its package, the reference's first passing one
-// (Robot.cpp:313-498). A line whose winner is not its guess stops the run there (*next_out = that
-// line; L + 1 when a workgroup's exchange timed out: the scan is abandoned): the caller continues
-// with the per-line phases from the state after the lines before it. Every rank holds the same
-// replicated state, so every rank stops at the same line.
-template <typename T>
-__global__ __launch_bounds__(SHR_THREADS) void shard_run_kernel(ShardParams p)
-{
-    __shared__ int sh_cw[SC_WORDS];
-    __shared__ double sh_rob[12];
-    __shared__ double sh_pkg[MB_WORDS_FIXED + 4 * EKF_MAX_LINES];
-    __shared__ int sh_best[SHR_GMAX];
-    __shared__ int sh_to;
-    __shared__ int sh_bad;   // workgroup 0: some workgroup timed out, never arrived or stopped elsewhere
-    __shared__ double sh_slot[SHR_THREADS][SH_PKG_WORDS];   // each thread's package of its passing landmark
-    const int tid = threadIdx.x, g = blockIdx.x, G = gridDim.x;
-    for (int k = tid; k < SC_WORDS; k += SHR_THREADS) sh_cw[k] = p.ctl[k];
-    if (tid < 12) sh_rob[tid] = p.rob[tid];
-    if (tid == 0) sh_to = sh_bad = 0;
-    __syncthreads();
-    ShardParams q = p;
-    q.ctl = sh_cw;
-    q.rob = sh_rob;
-    q.pkg = sh_pkg;
-    PllView<T> pv = {};   // (unused by the per-line phases)
-    const int N = p.d.N;
-    const int stride = G * SHR_THREADS;
-    // one landmark per thread: every passing landmark builds its package during the gate (the
-    // owner's slot is the package); otherwise the owner rebuilds it after the gate (SH_PACKAGE)
-    const bool fused = N <= stride;
-    q.pkg_slot = fused ? &sh_slot[0][0] : nullptr;   // (only SH_GATE reads it: its thread's row)
-    int status = 0, i = 0;
-    for (; i < p.L; i++) {
-        for (int j = g * SHR_THREADS + tid; j < N; j += stride) shard_step<T>(q, SH_GATE, i, j, pv);
-        __syncthreads();
-        const int lw = sh_cw[SC_WIN];   // this workgroup's first passing landmark
-        const int m = sh_cw[SC_M];
-        const double* lpk = sh_pkg;
-        if (fused) {
-            if (lw != 0x7fffffff) lpk = sh_slot[lw % SHR_THREADS];
-        } else {
-            if (lw != 0x7fffffff && lw % SHR_THREADS == tid) shard_step<T>(q, SH_PACKAGE, i, lw, pv);
-            __syncthreads();
-        }
-        // to the mailbox (parity i & 1: a workgroup one line ahead never overwrites a slot that
-        // another still reads), drained and ordered by the barrier before the tagged word
-        double* slot = p.mbox + ((size_t)(i & 1) * G + g) * p.mbw;
-        const int npk = MB_VH + 4 * m;
-        if (lw != 0x7fffffff)
-            for (int k = 1 + tid; k < npk; k += SHR_THREADS) mb_store(slot + k, lpk[k]);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) mb_tag(slot, p.epoch, (unsigned)(i + 1), (unsigned)(lw == 0x7fffffff ? 0 : lw + 1));
-        for (int k = tid; k < G; k += SHR_THREADS) {
-            const int bq = mb_poll(p.mbox, i & 1, G, k, p.mbw, p.epoch, (unsigned)(i + 1), status, p.spin_log2);
-            if (bq < 0) sh_to = 1;
-            sh_best[k] = bq <= 0 ? 0x7fffffff : bq - 1;
-        }
-        __syncthreads();
-        if (sh_to) break;   // (uniform in the workgroup)
-        int w = 0x7fffffff, gw = 0;
-        for (int k = 0; k < G; k++)
-            if (sh_best[k] < w) {
-                w = sh_best[k];
-                gw = k;
-            }
-        if (w != 0x7fffffff && w != sh_cw[SC_GUESS + i]) break;   // (uniform)
-        if (w != 0x7fffffff && gw != g) {
-            const double* ws = p.mbox + ((size_t)(i & 1) * G + gw) * p.mbw;
-            for (int k = 1 + tid; k < npk; k += SHR_THREADS) sh_pkg[k] = mb_load(ws + k);
-        } else if (w != 0x7fffffff && fused) {
-            for (int k = 1 + tid; k < npk; k += SHR_THREADS) sh_pkg[k] = lpk[k];
-        }
-        if (tid == 0) sh_cw[SC_WIN] = w;
-        q.col = p.cols + 4 * (size_t)i * N;
-        __syncthreads();
-        for (int j = g * SHR_THREADS + tid; j < N; j += stride) shard_step<T>(q, SH_APPLY, i, j, pv);
-        __syncthreads();
-        if (tid == 0) shard_step<T>(q, SH_ROBOT, i, 0, pv);
-        __syncthreads();
-    }
-    // every workgroup's outcome to workgroup 0: its stopping line and whether one of its exchanges
-    // timed out, one self-tagged word each (parity-0 slot, last word: the list words' region, which
-    // the association kernel of a partitioned context never uses). Workgroup 0 decides the stopping
-    // line over all G of them, so a workgroup that timed out — its landmarks then missed the line it
-    // broke at, possibly the last one, which workgroup 0 completed — or never arrived makes the run
-    // report L + 1, and the scan is abandoned on every rank
-    if (tid == 0)
-        mb_store_tagged(p.mbox + (size_t)g * p.mbw + p.mbw - 1, p.epoch,
-                        ((unsigned long long)i << 1) | (sh_to ? 1ull : 0ull));
-    if (g == 0) {
-        for (int k = tid; k < G; k += SHR_THREADS) {
-            int st = sh_to ? (int)EKF_ST_TIMEOUT_BIT : 0;   // (timed out already: no second wait)
-            const unsigned long long w =
-                mb_wait_tagged(p.mbox + (size_t)k * p.mbw + p.mbw - 1, p.epoch, st, p.spin_log2);
-            if (st || (w & 1ull) || (int)(w >> 1) != i) atomicOr(&sh_bad, 1);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            sh_cw[SC_NEXT] = i;
-            *p.next_out = (sh_to || sh_bad) ? (double)(p.L + 1) : (double)i;
-        }
-    }
-    __syncthreads();
-    // the status bits of every workgroup's landmarks (each copy started from the same word)
-    if (tid == 0) atomicOr(p.ctl + SC_STATUS, sh_cw[SC_STATUS] | (sh_to ? (int)EKF_ST_TIMEOUT_BIT : 0));
-    if (g == 0) {
-        for (int k = tid; k < SC_WORDS; k += SHR_THREADS)
-            if (k != SC_STATUS) p.ctl[k] = sh_cw[k];
-        if (tid < 12) p.rob[tid] = sh_rob[tid];
-    }
-}
-
-// The speculative path's lines in the association kernel's form (ekf_shard_run with
-// at most SH_MAX_LINES lines; K = ⌈N / (G·SHR_THREADS)⌉ landmarks per thread): instead of one
-// exchange among the workgroups per line, every workgroup replays the guessed winners' chain itself
-// from the exchanged guessed columns (p.cols, which hold every block (j, w_t), the winners' mutual
-// blocks among them) and checks each line's guess on its own landmarks; one verdict exchange at the
-// end. Per workgroup: two landmark waves (one landmark per thread, its record, history rows and
-// flags kept in registers and LDS) and a replay wave (lane u = line u's guessed winner). Line t:
-// the replay lane t evaluates its winner's gate at the state after lines < t (shard_step's
-// SH_GATE sequence) and, if it passes, builds the line's package (build_package and the winner's
-// V rows of the earlier matches, as SH_PACKAGE); every lane takes the robot update
-// (robot_update, as SH_ROBOT) and the later winners' lanes apply the line to their winners (gain
-// rows, as SH_APPLY). Meanwhile each landmark thread, per line as its package is published:
-// its gate at that state (SH_GATE), a violation if it passes before the guess or while the guess
-// fails, and the line's update (SH_APPLY: gain rows, history row, operand rows). The verdict (the
-// first violating line over all workgroups) decides: the records, flags, history rows, control
-// words and robot block are written as they stand after the lines before it (recomputed from the
-// run's start when a violation cut the lines short), and *next_out = that line; the caller runs
-// the per-line phases from there, as after shard_run_kernel. With several landmarks per thread
-// (N > G·SHR_THREADS) each thread checks its landmarks one after the other without stores, and
-// after the verdict runs each again over the lines kept, with the stores. Every value comes from
-// the same functions on the same inputs as the per-line phases: bit-identical.
-constexpr int SPR_THREADS = SHR_THREADS + 64;   // two landmark waves + the replay wave
-template <typename T>
-__global__ __launch_bounds__(SPR_THREADS) void shard_spec_kernel(ShardParams p)
-{
-    using C = typename Stor<T>::C;
-    constexpr double ETA = gate_eta<T>();
-    constexpr int SPK = MB_VH + 4 * SH_MAX_LINES;   // a package: build_package's words + the V rows
-    __shared__ int sh_cw[SC_WORDS];
-    __shared__ double sh_pk[SH_MAX_LINES][SPK];          // line t's package
-    __shared__ double sh_robl[SH_MAX_LINES + 1][12];     // the robot block and x_pre before line t
-    __shared__ int sh_pass[SH_MAX_LINES];                // line t's guessed winner passed its gate
-    __shared__ int sh_ready;                              // packages published (lines < sh_ready)
-    __shared__ double sh_wh[SH_MAX_LINES][SH_MAX_LINES][8];   // replay lane u: winner u's history rows
-    __shared__ double sh_lh[SH_MAX_LINES][4][SHR_THREADS];    // landmark thread tid: its U rows
-    __shared__ int sh_red[SPR_THREADS / 64];
-    __shared__ int sh_to, sh_bad, sh_first;
-    const int tid = threadIdx.x, g = blockIdx.x, G = gridDim.x;
-    const Dims d = p.d;
-    const int N = d.N, L = p.L;
-    const bool sym = p.r_mode != 1 && sizeof(C) == 4;
-    for (int k = tid; k < SC_WORDS; k += SPR_THREADS) sh_cw[k] = p.ctl[k];
-    if (tid < 12) sh_robl[0][tid] = p.rob[tid];
-    if (tid == 0) {
-        sh_ready = 0;
-        sh_to = sh_bad = 0;
-        sh_first = L;
-    }
-    __syncthreads();
-    const int s = sh_cw[SC_S];
-    int tstatus = 0;
-
-    // the operand rows of match m of landmark j (SH_APPLY's stores)
-    auto store_ops = [&](int j, int m, const double (&kk)[4], const double (&uu)[4], const float (&F)[3]) {
-        C* Uop = reinterpret_cast<C*>(p.cur.Uop);
-        C* Vop = reinterpret_cast<C*>(p.cur.Vop);
-#pragma unroll
-        for (int pp = 0; pp < 2; pp++) {
-            const int lr = 2 * j + pp;
-            if constexpr (sizeof(C) == 4) {
-                double o0 = uu[2 * pp], o1 = uu[2 * pp + 1], v0 = kk[2 * pp], v1 = kk[2 * pp + 1];
-                if (sym) {
-                    v0 = kk[2 * pp] * (double)F[0] + kk[2 * pp + 1] * (double)F[1];
-                    v1 = kk[2 * pp + 1] * (double)F[2];
-                    o0 = (double)(float)v0;
-                    o1 = (double)(float)v1;
-                }
-                Uop[op_index_f32(lr, 2 * m, d.kmax)] = to_domain<T>(-o0, 0);
-                Uop[op_index_f32(lr, 2 * m + 1, d.kmax)] = to_domain<T>(-o1, 0);
-                Vop[op_index_f32(lr, 2 * m, d.kmax)] = (C)v0;
-                Vop[op_index_f32(lr, 2 * m + 1, d.kmax)] = (C)v1;
-            } else {
-                Uop[op_index_f64(lr, 2 * m, d.kmax)] = (C)(-uu[2 * pp]);
-                Uop[op_index_f64(lr, 2 * m + 1, d.kmax)] = (C)(-uu[2 * pp + 1]);
-                Vop[op_index_f64(lr, 2 * m, d.kmax)] = (C)kk[2 * pp];
-                Vop[op_index_f64(lr, 2 * m + 1, d.kmax)] = (C)kk[2 * pp + 1];
-            }
-        }
-    };
-    // the gate of one landmark at the robot state rob (SH_GATE's evaluation)
-    auto gate_of = [&](const double* rob, const double2& rr0, const double2& rr1, const double2& rr2,
-                       const double2& yb, const double (&Dj)[4], const double* rc, int line, Cand& c, bool& pass,
-                       bool& sing, bool& amb) {
-        const ekf_line ln = p.lines[line];
-        double Rm[4];
-        line_R(ln, line, p.r_mode, Rm);
-        double R33[9], xp[3];
-#pragma unroll
-        for (int a = 0; a < 9; a++) R33[a] = rob[a];
-        xp[0] = rob[9]; xp[1] = rob[10]; xp[2] = rob[11];
-        Block5 b5;
-        fill_block5(b5, R33, rr0, rr1, rr2, Dj);
-        double sn, cs;
-        pass = sing = amb = false;
-        if (!quick_reject(b5, yb.x, yb.y, rc[12], rc[15], rc[16], xp, ln.alpha, ln.r, Rm, p.gate, ETA) &&
-            (sincos_near(yb.x, rc[12], rc[13], rc[14], sn, cs),
-             !certified_reject(b5, yb.x, yb.y, sn, cs, xp, ln.alpha, ln.r, Rm, p.gate, ETA))) {
-            eval_candidate(b5, yb.x, yb.y, sn, cs, xp, ln.alpha, ln.r, Rm, p.gate, ETA, c);
-            sing = c.singular;
-            amb = c.amb;
-            pass = c.pass;
-        }
-    };
-
-    if (tid >= SHR_THREADS) {
-        // ---- the replay wave: lane u carries line u's guessed winner up to its line ----
-        const int u = tid - SHR_THREADS;
-        const int wu = u < L ? sh_cw[SC_GUESS + u] : 0x7fffffff;
-        const bool act = wu != 0x7fffffff && wu < N;
-        double rc[SH_REC];
-        if (act)
-            for (int k = 0; k < SH_REC; k++) rc[k] = p.rec[(size_t)wu * SH_REC + k];
-        else
-            for (int k = 0; k < SH_REC; k++) rc[k] = 0.0;
-        double2 rr0 = make_double2(rc[0], rc[1]), rr1 = make_double2(rc[2], rc[3]), rr2 = make_double2(rc[4], rc[5]);
-        double2 yb = make_double2(rc[6], rc[7]);
-        double Dj[4] = {rc[8], rc[9], rc[10], rc[11]};
-        bool matched = false;
-        int m = 0;
-        for (int t = 0; t < L; t++) {
-            const int wt = sh_cw[SC_GUESS + t];
-            bool pass = false;
-            if (u == t && act && !matched && wu < s) {
-                // the exact evaluation without the reject filters, which never reject a landmark
-                // that passes (the association kernel's replay wave does the same); its status
-                // bits come from the landmark's own thread
-                Cand c;
-                const ekf_line ln = p.lines[t];
-                double Rm[4];
-                line_R(ln, t, p.r_mode, Rm);
-                double R33[9], xp[3];
-#pragma unroll
-                for (int a = 0; a < 9; a++) R33[a] = sh_robl[t][a];
-                xp[0] = sh_robl[t][9]; xp[1] = sh_robl[t][10]; xp[2] = sh_robl[t][11];
-                Block5 b5;
-                fill_block5(b5, R33, rr0, rr1, rr2, Dj);
-                double sn, cs;
-                sincos_near(yb.x, rc[12], rc[13], rc[14], sn, cs);
-                eval_candidate<false>(b5, yb.x, yb.y, sn, cs, xp, ln.alpha, ln.r, Rm, p.gate, ETA, c);
-                pass = c.pass;
-                if (pass) {
-                    build_package(c, R33, rr0, rr1, rr2, sh_pk[t]);
-                    for (int q = 0; q < m; q++)
-#pragma unroll
-                        for (int k = 0; k < 4; k++) sh_pk[t][MB_VH + 4 * q + k] = sh_wh[u][q][4 + k];
-                }
-                sh_pass[t] = pass ? 1 : 0;
-            } else if (u == t) {
-                sh_pass[t] = 0;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            const bool pt = sh_pass[t] != 0;
-            // the robot block and x_pre after line t (SH_ROBOT; every lane the same bits)
-            {
-                double R33[9], xp[3];
-#pragma unroll
-                for (int a = 0; a < 9; a++) R33[a] = sh_robl[t][a];
-                xp[0] = sh_robl[t][9]; xp[1] = sh_robl[t][10]; xp[2] = sh_robl[t][11];
-                if (pt) robot_update(R33, xp, sh_pk[t]);
-                if (u == 0) {
-#pragma unroll
-                    for (int a = 0; a < 9; a++) sh_robl[t + 1][a] = R33[a];
-                    sh_robl[t + 1][9] = xp[0]; sh_robl[t + 1][10] = xp[1]; sh_robl[t + 1][11] = xp[2];
-                }
-            }
-            // the later winners take line t's update (SH_APPLY on their own landmark)
-            if (pt && act && u > t) {
-                const double4 cb = *reinterpret_cast<const double4*>(p.cols + 4 * ((size_t)t * N + wu));
-                double blk[4] = {cb.x, cb.y, cb.z, cb.w};
-                const double* pk = sh_pk[t];
-                double kk[4], uu[4];
-                gain_rows<0>(pk, m,
-                             [&](int q) { return make_double4(sh_wh[u][q][0], sh_wh[u][q][1], sh_wh[u][q][2], sh_wh[u][q][3]); },
-                             [&](int q) {
-                                 const double* vh = pk + MB_VH + 4 * q;
-                                 return make_double4(vh[0], vh[1], vh[2], vh[3]);
-                             },
-                             blk, rr0, rr1, rr2, yb, Dj, kk, uu);
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    sh_wh[u][m][k] = uu[k];
-                    sh_wh[u][m][4 + k] = kk[k];
-                }
-                if (wu == wt) matched = true;
-            }
-            if (pt) m++;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            if (u == 0) __hip_atomic_store(&sh_ready, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-    }
-
-    // ---- the landmark waves: landmark j = g·SHR_THREADS + tid + k·G·SHR_THREADS, k < K ----
-    const int K = (N + G * SHR_THREADS - 1) / (G * SHR_THREADS);   // landmarks per thread (uniform)
-    const int j0 = g * SHR_THREADS + tid;
-    int stacc = 0;   // the status bits of the lines run (SH_APPLY's)
-    int viol = L;    // this thread's first violating line
-    // one pass over lines [0, upto) for landmark j: gates (check: the violations), updates into
-    // the registers; store: the history and operand rows as they come (the same rows are
-    // rewritten by the per-line phases for any line not kept)
-    auto run_lines = [&](int j, const double* rc, int upto, bool check, bool store, double2& rr0, double2& rr1,
-                         double2& rr2, double2& yb, double (&Dj)[4], bool& matched, int& m) {
-        const bool own = tid < SHR_THREADS && j < N;
-        for (int i = 0; i < upto; i++) {
-            if (tid < SHR_THREADS) {
-                int polls = 0;
-                while (__hip_atomic_load(&sh_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= i) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if ((tstatus & EKF_ST_TIMEOUT_BIT) || ++polls > (1 << p.spin_log2)) {
-                        tstatus |= EKF_ST_TIMEOUT_BIT;
-                        break;
-                    }
-                }
-            }
-            if (!own) continue;
-            const int w = sh_cw[SC_GUESS + i];
-            const bool pt = sh_pass[i] != 0;
-            const int jstar = pt ? w : 0x7fffffff;
-            bool pass = false, sing = false, amb = false;
-            if (j < s && !matched) {
-                Cand c;
-                gate_of(sh_robl[i], rr0, rr1, rr2, yb, Dj, rc, i, c, pass, sing, amb);
-            }
-            if (check && pass && (!pt || j < w)) {   // the guess is not the line's first passing landmark
-                viol = min(viol, i);
-                return;
-            }
-            int st = sing && j <= jstar ? (int)EKF_ST_SINGULAR : 0;
-            if (amb && j <= jstar) st |= EKF_ST_PRECISION_BIT;
-            if (p.r_mode == 1 && (i == 1 || i == 2)) st |= EKF_ST_NSYM;
-            stacc |= st;
-            if (!pt) continue;
-            const double4 cb = *reinterpret_cast<const double4*>(p.cols + 4 * ((size_t)i * N + j));
-            double blk[4] = {cb.x, cb.y, cb.z, cb.w};
-            const double* pk = sh_pk[i];
-            double kk[4], uu[4];
-            gain_rows<0>(pk, m,
-                         [&](int q) { return make_double4(sh_lh[q][0][tid], sh_lh[q][1][tid], sh_lh[q][2][tid], sh_lh[q][3][tid]); },
-                         [&](int q) {
-                             const double* vh = pk + MB_VH + 4 * q;
-                             return make_double4(vh[0], vh[1], vh[2], vh[3]);
-                         },
-                         blk, rr0, rr1, rr2, yb, Dj, kk, uu);
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                sh_lh[m][k][tid] = uu[k];
-            }
-            if (store) {
-                float F[3] = {0.f, 0.f, 0.f};
-                if (sym) sym_factor(pk, F);
-                double* h = p.hist + ((size_t)j * d.max_lines + m) * 8;   // (SH_APPLY's history row)
-                h[0] = uu[0]; h[1] = uu[1]; h[2] = uu[2]; h[3] = uu[3];
-                h[4] = kk[0]; h[5] = kk[1]; h[6] = kk[2]; h[7] = kk[3];
-                store_ops(j, m, kk, uu, F);
-            }
-            if (j == w) matched = true;
-            m++;
-        }
-    };
-    // one landmark's pass from its record at the run's start (the run starts at line 0:
-    // ekf_shard_run, no match yet), its record and flag written at the end (write)
-    auto run_landmark = [&](int j, int upto, bool check, bool store, bool write) {
-        const bool own = tid < SHR_THREADS && j < N;
-        double rc[SH_REC];
-        for (int k = 0; k < SH_REC; k++) rc[k] = own ? p.rec[(size_t)j * SH_REC + k] : 0.0;
-        double2 rr0 = make_double2(rc[0], rc[1]), rr1 = make_double2(rc[2], rc[3]), rr2 = make_double2(rc[4], rc[5]);
-        double2 yb = make_double2(rc[6], rc[7]);
-        double Dj[4] = {rc[8], rc[9], rc[10], rc[11]};
-        bool matched = own && (p.flags[j] & 1);
-        int m = 0;
-        run_lines(j, rc, upto, check, store, rr0, rr1, rr2, yb, Dj, matched, m);
-        if (write && own) {
-            double* r = p.rec + (size_t)j * SH_REC;
-            const double v[12] = {rr0.x, rr0.y, rr1.x, rr1.y, rr2.x, rr2.y, yb.x, yb.y, Dj[0], Dj[1], Dj[2], Dj[3]};
-            for (int k = 0; k < 12; k++) r[k] = v[k];
-            p.flags[j] = matched ? 1 : 0;
-        }
-    };
-    // one landmark per thread (K = 1): its state stays in registers across the verdict and is
-    // recomputed only when a violation cut the run short
-    double2 rr0 = make_double2(0, 0), rr1 = rr0, rr2 = rr0, yb = rr0;
-    double Dj[4] = {0, 0, 0, 0};
-    bool matched = false;
-    int m = 0;
-    double rc0[SH_REC];
-    const bool own0 = tid < SHR_THREADS && j0 < N;
-    if (K == 1) {
-        for (int k = 0; k < SH_REC; k++) rc0[k] = own0 ? p.rec[(size_t)j0 * SH_REC + k] : 0.0;
-        rr0 = make_double2(rc0[0], rc0[1]); rr1 = make_double2(rc0[2], rc0[3]); rr2 = make_double2(rc0[4], rc0[5]);
-        yb = make_double2(rc0[6], rc0[7]);
-        Dj[0] = rc0[8]; Dj[1] = rc0[9]; Dj[2] = rc0[10]; Dj[3] = rc0[11];
-        matched = own0 && (p.flags[j0] & 1);
-        run_lines(j0, rc0, L, true, true, rr0, rr1, rr2, yb, Dj, matched, m);
-    } else {
-        // several landmarks per thread: check each in turn (no stores; lines at or past an earlier
-        // violation of this thread are never kept), the stores after the verdict
-        for (int k = 0; k < K; k++) run_landmark(j0 + k * G * SHR_THREADS, viol, true, false, false);
-    }
-    // ---- the verdict: the first violating line over every workgroup (one exchange) ----
-    {
-        int v = viol;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
-        if ((tid & 63) == 0) sh_red[tid >> 6] = v;
-        __syncthreads();
-        int wv = L;
-        for (int w = 0; w < SHR_THREADS / 64; w++) wv = min(wv, sh_red[w]);
-        double* slot = p.mbox + (size_t)g * p.mbw;
-        if (tid == 0) mb_tag(slot, p.epoch, TAG_SPEC_VERDICT, (unsigned)(wv + 1));
-        for (int k = tid; k < G; k += SPR_THREADS) {
-            const int bq = mb_poll(p.mbox, 0, G, k, p.mbw, p.epoch, TAG_SPEC_VERDICT, tstatus, p.spin_log2);
-            if (bq <= 0) sh_to = 1;
-            else atomicMin(&sh_first, bq - 1);
-        }
-        if (tstatus & EKF_ST_TIMEOUT_BIT) sh_to = 1;
-        __syncthreads();
-    }
-    const int first = sh_to ? 0 : sh_first;
-    if (K == 1) {
-        // the state after the lines before `first` (recomputed when the run was cut short)
-        if (first < L && !sh_to) {
-            rr0 = make_double2(rc0[0], rc0[1]); rr1 = make_double2(rc0[2], rc0[3]); rr2 = make_double2(rc0[4], rc0[5]);
-            yb = make_double2(rc0[6], rc0[7]);
-            Dj[0] = rc0[8]; Dj[1] = rc0[9]; Dj[2] = rc0[10]; Dj[3] = rc0[11];
-            matched = own0 && (p.flags[j0] & 1);
-            m = 0;
-            stacc = 0;
-            run_lines(j0, rc0, first, false, true, rr0, rr1, rr2, yb, Dj, matched, m);
-        }
-        if (own0 && !sh_to) {
-            double* r = p.rec + (size_t)j0 * SH_REC;
-            const double v[12] = {rr0.x, rr0.y, rr1.x, rr1.y, rr2.x, rr2.y, yb.x, yb.y, Dj[0], Dj[1], Dj[2], Dj[3]};
-            for (int k = 0; k < 12; k++) r[k] = v[k];
-            p.flags[j0] = matched ? 1 : 0;
-        }
-    } else if (!sh_to) {
-        stacc = 0;
-        for (int k = 0; k < K; k++) run_landmark(j0 + k * G * SHR_THREADS, first, false, true, true);
-    }
-    const bool own = own0 || (K > 1 && tid < SHR_THREADS);
-    int st = own ? stacc : 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) st |= __shfl_xor(st, off, 64);
-    __syncthreads();
-    if ((tid & 63) == 0) sh_red[tid >> 6] = st;
-    __syncthreads();
-    // every workgroup's outcome to workgroup 0 (as shard_run_kernel): a workgroup whose verdict
-    // poll timed out makes the run report L + 1, and the scan is abandoned on every rank
-    if (tid == 0) {
-        int wst = 0;
-        for (int w = 0; w < SPR_THREADS / 64; w++) wst |= sh_red[w];
-        atomicOr(p.ctl + SC_STATUS, wst | (sh_to ? (int)EKF_ST_TIMEOUT_BIT : 0));
-        mb_store_tagged(p.mbox + (size_t)g * p.mbw + p.mbw - 1, p.epoch,
-                        ((unsigned long long)first << 1) | (sh_to ? 1ull : 0ull));
-    }
-    if (g == 0) {
-        for (int k = tid; k < G; k += SPR_THREADS) {
-            int stw = sh_to ? (int)EKF_ST_TIMEOUT_BIT : 0;
-            const unsigned long long w = mb_wait_tagged(p.mbox + (size_t)k * p.mbw + p.mbw - 1, p.epoch, stw, p.spin_log2);
-            if (stw || (w & 1ull) || (int)(w >> 1) != first) atomicOr(&sh_bad, 1);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            // the control words after the lines kept (SH_ROBOT's bookkeeping, line by line)
-            int mm = 0, nx = sh_cw[SC_NEXTRA];
-            for (int i = 0; i < first; i++) {
-                if (sh_pass[i]) {
-                    sh_cw[SC_MATCH + i] = sh_cw[SC_GUESS + i];
-                    mm++;
-                } else {
-                    sh_cw[SC_MATCH + i] = -1;
-                    sh_cw[SC_EXTRA + nx] = i;
-                    nx++;
-                }
-            }
-            sh_cw[SC_M] += mm;
-            sh_cw[SC_NEXTRA] = nx;
-            sh_cw[SC_WIN] = 0x7fffffff;
-            sh_cw[SC_NEXT] = first;
-            *p.next_out = (sh_to || sh_bad) ? (double)(L + 1) : (double)first;
-        }
-        __syncthreads();
-        for (int k = tid; k < SC_WORDS; k += SPR_THREADS)
-            if (k != SC_STATUS) p.ctl[k] = sh_cw[k];
-        if (tid < 12) p.rob[tid] = sh_robl[first][tid];
     }
 }
 

@@ -1,5 +1,5 @@
 // unit_shard_pack.hip — the partitioned instance's kernels, pack / unpack and the low-rank start.
-#include "ekf_kernels.hip"
+#include "ekf_shard_kernels.h"
 #include "ekf_pack.h"
 
 namespace ekf {
@@ -7,16 +7,10 @@ namespace ekf {
 hipError_t launch_shard_run(const ShardParams& p, int precision, hipStream_t st)
 {
     const unsigned G = (unsigned)shard_run_workgroups(p.d.N);
-    // at most SH_MAX_LINES lines: one verdict exchange for the run (shard_spec_kernel); otherwise
-    // one exchange per line (shard_run_kernel)
-    if (EKF_SHARD_SPEC && p.L <= SH_MAX_LINES && p.d.max_lines <= SH_MAX_LINES) {
-        if (precision == EKF_PREC_F64) hipLaunchKernelGGL(shard_spec_kernel<double>, dim3(G), dim3(SPR_THREADS), 0, st, p);
-        else if (precision == EKF_PREC_F32) hipLaunchKernelGGL(shard_spec_kernel<float>, dim3(G), dim3(SPR_THREADS), 0, st, p);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-    }
-    if (precision == EKF_PREC_F64) hipLaunchKernelGGL(shard_run_kernel<double>, dim3(G), dim3(SHR_THREADS), 0, st, p);
-    else if (precision == EKF_PREC_F32) hipLaunchKernelGGL(shard_run_kernel<float>, dim3(G), dim3(SHR_THREADS), 0, st, p);
+    // shard_spec_kernel's LDS holds SH_MAX_LINES lines (ekf_shard_create admits no more)
+    if (p.L > SH_MAX_LINES || p.d.max_lines > SH_MAX_LINES) return hipErrorInvalidValue;
+    if (precision == EKF_PREC_F64) hipLaunchKernelGGL(shard_spec_kernel<double>, dim3(G), dim3(SPR_THREADS), 0, st, p);
+    else if (precision == EKF_PREC_F32) hipLaunchKernelGGL(shard_spec_kernel<float>, dim3(G), dim3(SPR_THREADS), 0, st, p);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
