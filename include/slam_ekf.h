@@ -43,7 +43,8 @@ extern "C" {
  *    ekf_gate_joint, ekf_gate_joint_device; ekf_resample, ekf_copy_instance;
  *    ekf_instance_image_bytes, ekf_export_instances(_device), ekf_import_instances(_device);
  *    ekf_associate_joint, ekf_associate_joint_device; ekf_gate_candidates_device,
- *    ekf_assoc_weights_device, ekf_resample_plan_device, ekf_resample_device. */
+ *    ekf_assoc_weights_device, ekf_resample_plan_device, ekf_resample_device; ekf_gate_landmarks,
+ *    ekf_gate_landmarks_device. */
 #define SLAM_EKF_ABI_VERSION 3
 #define EKF_MAX_LINES 64 /* lines per scan per instance; main.cpp:99 reserves 20 */
 
@@ -375,6 +376,61 @@ int ekf_gate_lines(ekf_ctx* ctx, int e, const double enc[3] /* may be NULL */, c
 int ekf_gate_lines_device(ekf_ctx* ctx, const double* d_enc /* [E][3] or NULL */,
                           const ekf_line* d_lines /* [E][max_lines] */, const int32_t* d_nlines /* [E] */,
                           ekf_gate_hit* d_hits /* [E][max_lines] */, double* d_d2 /* [E][max_lines][N] or NULL */);
+
+/* Landmark pairs that are one line, state untouched: every saved landmark scored against every other.
+ * The reference's association is first-fit (Robot.cpp:313-498) and appends a line that misses its gate
+ * as a new landmark (Robot.cpp:776-866), so a map collects landmarks that are one physical line; a wall
+ * seen from both sides is stored twice by construction, as (alpha, r) and (alpha + pi, -r). Its only
+ * remedy is to wipe the map (Robot.cpp:893-904). This call finds the pairs; it does not act on them.
+ * The pair (lo, hi): lo = min(a, b), hi = max(a, b), whichever side asks, both below savedLineCount, so
+ *   d2[a][b] == d2[b][a] bit for bit.
+ * Blocks: Dlo, Dhi the two diagonal 2x2 blocks, X = P[lo, hi], each read as the covariance queries read
+ *   it: the pending steps of the flush group applied on read and, with fp16 storage on the split
+ *   arithmetics, the group's one to-storage rounding. With EKF_ARITH_EXACT and on fp64 storage these are
+ *   the bits ekf_download_state would show; on the split arithmetics the exact per-element chain, as for
+ *   the queries. The mean is the committed copy of y.
+ * Same-direction form, additions only, in this order:
+ *   c00 = (Dlo00 + Dhi00) - (X00 + X00), c01 = (Dlo01 + Dhi01) - (X01 + X10),
+ *   c11 = (Dlo11 + Dhi11) - (X11 + X11), d0 = remainder(alpha_lo - alpha_hi, 2 pi) (the IEEE
+ *   remainder, 2 pi the fp64 constant), d1 = r_lo - r_hi.
+ * Flipped form (hi taken as (alpha_hi + pi, -r_hi), F = diag(1, -1)): c00 as above,
+ *   c01 = (Dlo01 - Dhi01) + (X01 - X10), c11 = (Dlo11 + Dhi11) + (X11 + X11),
+ *   d0 = remainder((alpha_lo - alpha_hi) - pi, 2 pi), d1 = r_lo + r_hi.
+ * Distance of one form: Cholesky in fp64 in a fixed order, a*b + c contracted within one expression:
+ *   l00 = sqrt(c00), l10 = c01 / l00, t = c11 - l10 l10, l11 = sqrt(t), z0 = d0 / l00,
+ *   z1 = (d1 - l10 z0) / l11, d2 = z0 z0 + z1 z1. A form whose c00 or t is <= 0 or not finite is NaN.
+ * Distance of the pair: the same-direction value when the flipped one is NaN or the same-direction one
+ *   is <= it, else the flipped value. Both NaN: the pair is NaN and EKF_PH_SINGULAR is set in the
+ *   records of both lo and hi.
+ * Pass: d2 <= gate * gate; a NaN fails, as in ekf_associate_joint.
+ * The matrix d2 [N][N]: the pair's value for two different saved landmarks; +inf on the diagonal and
+ *   where either index is at or past savedLineCount.
+ * The records: hits[a] is a pure function of row a of that matrix, whether or not the matrix is
+ *   requested: first the lowest passing index, npass the count of passing entries, nearest the argmin
+ *   over the finite entries (lowest index on ties). EKF_PH_FLIP_* says that the reported pair's value is
+ *   the flipped form's. A landmark at or past savedLineCount, or a map with fewer than two landmarks,
+ *   gets the empty record: -1, -1, 0, 0, NaN, NaN, zeros.
+ * No drain, no state change, as ekf_gate_lines: nothing of the state, the schedule, the step count or
+ *   the result mirror is written. Valid at any point, also between ekf_predict and ekf_update: the
+ *   predict moves neither the landmark block nor the landmark means. The host form is synchronous (two
+ *   kernels, one copy, one wait on the context stream) and gives the same bits as the device form,
+ *   which only enqueues. The result does not depend on how the device schedules the work: every
+ *   reduction is over a total order (min index, integer sum, min of (d2, index)).
+ * Errors: EKF_EINVAL for a NULL context, NULL hits, a gate that is not a finite number >= 0, or a
+ *   partitioned context (ekf_shard_create); EKF_ERANGE for e out of range. */
+enum { EKF_PH_FLIP_NEAREST = 1, EKF_PH_FLIP_FIRST = 2, EKF_PH_SINGULAR = 4 };   /* ekf_pair_hit.status */
+typedef struct ekf_pair_hit {      /* landmark a against every other saved landmark; 72 bytes */
+    int32_t nearest;   /* partner with the smallest d2 (lowest index on ties, NaN ignored); -1: none */
+    int32_t first;     /* lowest partner index whose d2 passes; -1: none */
+    int32_t npass;     /* partners that pass */
+    int32_t status;    /* EKF_PH_* */
+    double d2_nearest, d2_first;   /* NaN if none */
+    double C[3], delta[2];         /* c00, c01, c11 and delta of `nearest`, in the form that won; zeros if none */
+} ekf_pair_hit;
+int ekf_gate_landmarks(ekf_ctx* ctx, int e, double gate, ekf_pair_hit* hits /* [N] */, double* d2 /* [N][N], may be NULL */);
+/* Every instance at once, both buffers in device memory, asynchronous on the context stream. */
+int ekf_gate_landmarks_device(ekf_ctx* ctx, double gate, ekf_pair_hit* d_hits /* [E][N] */,
+                              double* d_d2 /* [E][N][N] or NULL */);
 
 /* Joint compatibility of line-landmark hypotheses, state untouched: the squared Mahalanobis distance
  * and the log determinant of the stacked innovation of a whole assignment. ekf_gate_lines scores each

@@ -81,7 +81,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-mllvm", "-amdgpu-mfma-vgpr-for
 # The compilation units, in link order (the order of the code objects in the library). Each
 # unit_*.hip includes the device code its kernels need (the flush units a header per flush family,
 # the query unit ekf_device.h alone, the gate unit ekf_gate.h, the joint and search units
-# ekf_joint_parts.h above it, the resample and image units only their tables' headers and the shared
+# ekf_joint_parts.h above it, the pairs unit ekf_pairs.h, the resample and image units only their tables' headers and the shared
 # copy body, the loop unit ekf_loop_plan.h alone, the three scan units the association kernel, ekf_kernels.hip,
 # which is not compiled on its own, and unit_shard_pack.hip the partitioned instance's kernels,
 # ekf_shard_kernels.h, with ekf_pack.h; those two share ekf_assoc_parts.h)
@@ -93,7 +93,8 @@ UNITS = ["unit_flush_f16x3.hip", "unit_flush_exact.hip", "unit_scan.hip", "unit_
          "unit_scan_nt64.hip", "unit_flush_2x4.hip", "unit_flush_bf16x6.hip", "unit_shard_pack.hip",
          "unit_flush_quad.hip", "unit_query.hip", "unit_gate.hip", "unit_joint.hip", "unit_assoc.hip",
          "ekf_api.hip", "ekf_state.hip", "ekf_shard.hip", "ekf_read.hip", "ekf_copy.hip",
-         "unit_resample.hip", "unit_image.hip", "unit_resample_device.hip", "unit_loop.hip"]
+         "unit_resample.hip", "unit_image.hip", "unit_resample_device.hip", "unit_loop.hip",
+         "unit_pairs.hip"]
 
 
 def source_deps(csrc: str = CSRC) -> list[str]:

@@ -3,7 +3,8 @@
 //   ekf_state.hip  the calls that read or write one instance's state without a scan: reset, upload,
 //                  download, low-rank initialisation, rescale, pose covariance, ellipse (ekf_ellipse.h);
 //   ekf_shard.hip  the partitioned instance: the ekf_shard_* protocol, RCCL, ekf_shard_localize;
-//   ekf_read.hip   the calls that read without draining: covariance queries, gate, joint gate, joint search;
+//   ekf_read.hip   the calls that read without draining: covariance queries, gate, joint gate, joint search,
+//                  landmark pairs;
 //   ekf_copy.hip   the calls that copy instances without draining: ekf_resample, the instance images.
 #pragma once
 
@@ -60,6 +61,9 @@ struct ekf_ctx {
     unsigned char* g_flags = nullptr;
     ekf::GatePart* g_part = nullptr;
     int predicted = 0;
+    // ekf_gate_landmarks: the partial records [E][N][⌈N/64⌉] of every landmark against every partner block
+    // (ekf_pairs.h PairParams; listed context memory, made on first use)
+    ekf_pair_hit* pr_part = nullptr;
     // ekf_associate_joint: the rows' plans, candidate and pair tables and the search workgroups' records
     // (ekf_kernels.h AssocParams; listed context memory, made on first use)
     ekf::AssocPlan* as_plan = nullptr;

@@ -1,7 +1,7 @@
 // ekf_read.hip — the calls that read the state without draining the flush (slam_ekf.h): the covariance
 // queries (ekf_query_*; kernel: unit_query.hip), the gate (ekf_gate_lines*; unit_gate.hip), the joint
-// gate (ekf_gate_joint*; unit_joint.hip) and the joint-compatibility search (ekf_associate_joint*;
-// unit_assoc.hip). Beside them the two stages of the hypothesis loop that read only what those calls wrote
+// gate (ekf_gate_joint*; unit_joint.hip), the joint-compatibility search (ekf_associate_joint*;
+// unit_assoc.hip) and the landmark pairs (ekf_gate_landmarks*; unit_pairs.hip). Beside them the two stages of the hypothesis loop that read only what those calls wrote
 // (ekf_gate_candidates_device, ekf_assoc_weights_device; unit_loop.hip): no view, no hazard handling.
 //
 // Each kernel takes the view the next association kernel would take in enqueue() (ReadView): X[base]
@@ -9,6 +9,7 @@
 // of the strip and the mean. It runs on S after every scan enqueued so far and changes nothing: no
 // flush, no step, no epoch. begin_read / end_read are the hazard handling.
 #include "ekf_ctx.h"
+#include "ekf_pairs.h"   // (PairParams, launch_pairs)
 
 static int begin_read(ekf_ctx* c, ekf::ReadView& v, ekf::Slot* pend)
 {
@@ -416,6 +417,68 @@ extern "C" int ekf_associate_joint_device(ekf_ctx* c, const double* d_enc, const
     ap.cand = d_cand;
     ap.hits = d_hits;
     return enqueue_assoc(c, ap);
+}
+
+// ---- landmark pairs (two launches on S; the partial records are the context's scratch) ----
+static int pairs_check(const ekf_ctx* c, int e, double gate, const ekf_pair_hit* hits)
+{
+    if (!c || c->sh_world > 0 || !hits) return EKF_EINVAL;
+    if (!(gate >= 0.0) || gate - gate != 0.0) return EKF_EINVAL;   // NaN, negative, +inf
+    if (e < 0 || e >= c->cfg.instances) return EKF_ERANGE;
+    return EKF_OK;
+}
+
+static int enqueue_pairs(ekf_ctx* c, ekf::PairParams& pp)
+{
+    if (!c->pr_part) {
+        void* pt = nullptr;
+        if (!dev_alloc(c, &pt, (size_t)c->cfg.instances * c->d.N * ekf::pair_blocks(c->d.N) * sizeof(ekf_pair_hit)))
+            return EKF_ENOMEM;
+        c->pr_part = (ekf_pair_hit*)pt;
+    }
+    const int rc = begin_read(c, pp.v, pp.pend);
+    if (rc) return rc;
+    pp.saved = c->saved;
+    pp.part = c->pr_part;
+    HIP_TRY(ekf::launch_pairs(pp, c->cfg.precision, c->stream));
+    return end_read(c);
+}
+
+extern "C" int ekf_gate_landmarks(ekf_ctx* c, int e, double gate, ekf_pair_hit* hits, double* d2)
+{
+    int rc = pairs_check(c, e, gate, hits);
+    if (rc) return rc;
+    // device scratch and the pinned buffer: [hits | d2]
+    const size_t N = (size_t)c->d.N;
+    const size_t nh = sizeof(ekf_pair_hit) * N;
+    const size_t nd = d2 ? sizeof(double) * N * N : 0;
+    rc = host_form(c, nh + nd, 0);
+    if (rc) return rc;
+    ekf::PairParams pp{};
+    pp.E = 1;
+    pp.e0 = e;
+    pp.gate = gate;
+    char* dev = reinterpret_cast<char*>(c->q_dev);
+    pp.hits = reinterpret_cast<ekf_pair_hit*>(dev);
+    pp.d2 = d2 ? reinterpret_cast<double*>(dev + nh) : nullptr;
+    rc = enqueue_pairs(c, pp);
+    if (!rc) rc = fetch_results(c, nh + nd);
+    if (rc) return rc;
+    memcpy(hits, c->q_pin.host, nh);
+    if (d2) memcpy(d2, c->q_pin.host + nh, nd);
+    return EKF_OK;
+}
+
+extern "C" int ekf_gate_landmarks_device(ekf_ctx* c, double gate, ekf_pair_hit* d_hits, double* d_d2)
+{
+    const int rc = pairs_check(c, 0, gate, d_hits);
+    if (rc) return rc;
+    ekf::PairParams pp{};
+    pp.E = c->cfg.instances;
+    pp.gate = gate;
+    pp.hits = d_hits;
+    pp.d2 = d_d2;
+    return enqueue_pairs(c, pp);
 }
 
 // ---- the loop's stages around the search: functions of the gate's matrix and of the hits, no filter state ----

@@ -44,7 +44,7 @@ EXPORTED = [
     "ekf_init_lowrank", "ekf_storage_exponent", "ekf_rescale", "ekf_get_pose_cov", "ekf_get_ellipse", "ekf_ellipse_of_block",
     "ekf_query_joint", "ekf_query_marginals", "ekf_query_joint_device",
     "ekf_gate_lines", "ekf_gate_lines_device", "ekf_gate_joint", "ekf_gate_joint_device",
-    "ekf_associate_joint", "ekf_associate_joint_device",
+    "ekf_associate_joint", "ekf_associate_joint_device", "ekf_gate_landmarks", "ekf_gate_landmarks_device",
     "ekf_resample", "ekf_copy_instance",
     "ekf_gate_candidates_device", "ekf_assoc_weights_device", "ekf_resample_plan_device", "ekf_resample_device",
     "ekf_instance_image_bytes", "ekf_export_instances", "ekf_import_instances",
@@ -103,6 +103,23 @@ class EkfJointHit(ctypes.Structure):
 
 
 ekf_joint_hit = EkfJointHit   # (the C name)
+
+PH_FLIP_NEAREST, PH_FLIP_FIRST, PH_SINGULAR = 1, 2, 4   # ekf_pair_hit.status
+
+
+class EkfPairHit(ctypes.Structure):
+    """ekf_pair_hit (slam_ekf.h): one landmark against every other saved landmark."""
+    _fields_ = [
+        ("nearest", ctypes.c_int32), ("first", ctypes.c_int32), ("npass", ctypes.c_int32),
+        ("status", ctypes.c_int32), ("d2_nearest", ctypes.c_double), ("d2_first", ctypes.c_double),
+        ("C", ctypes.c_double * 3), ("delta", ctypes.c_double * 2),
+    ]
+
+
+ekf_pair_hit = EkfPairHit   # (the C name)
+# the same record as a numpy structured type (Ensemble.gate_landmarks returns an array of it)
+PAIR_HIT_DTYPE = np.dtype([("nearest", "<i4"), ("first", "<i4"), ("npass", "<i4"), ("status", "<i4"),
+                           ("d2_nearest", "<f8"), ("d2_first", "<f8"), ("C", "<f8", (3,)), ("delta", "<f8", (2,))])
 
 ASSOC_MAX_CAND, ASSOC_MAX_LINES, ASSOC_MAX_TOTAL, ASSOC_MAX_NODES = 8, 16, 64, 1 << 22
 AS_TRUNCATED, AS_SINGULAR, AS_INVALID = 1, 2, 4   # ekf_assoc_hit.status
@@ -206,6 +223,8 @@ def load_library(path: str = ""):
         "ekf_associate_joint": (ctypes.c_int, [vp, ctypes.c_int, dp, vp, ctypes.c_int, vp, ctypes.c_int, dp,
                                                ctypes.c_int, vp]),
         "ekf_associate_joint_device": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]),
+        "ekf_gate_landmarks": (ctypes.c_int, [vp, ctypes.c_int, d, vp, dp]),
+        "ekf_gate_landmarks_device": (ctypes.c_int, [vp, d, vp, vp]),
         "ekf_resample": (ctypes.c_int, [vp, ip]),
         "ekf_copy_instance": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
         "ekf_gate_candidates_device": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, d, vp, vp]),
@@ -297,6 +316,45 @@ def gate_candidates(d2, C: int, gate: float) -> np.ndarray:
         ok = ok[np.argsort(row[ok], kind="stable")][:C]
         out[i, :len(ok)] = ok
     return out
+
+
+def duplicate_clusters(hits, d2=None) -> list[list[int]]:
+    """The landmark groups of size >= 2 that Ensemble.gate_landmarks' passing pairs connect (union-find),
+    each ascending, in ascending order of their lowest member. With the matrix d2 [N, N] every passing pair
+    is used: the passing partners of row a are its hits[a]["npass"] smallest entries (pass is a threshold on
+    d2, so no gate is needed). Without it only the pairs the records name, (a, first) and (a, nearest) where
+    something passes: a subset of the passing pairs, so a group may come out in parts. Host only."""
+    h = np.asarray(hits)
+    n = int(h.shape[0])
+    parent = list(range(n))
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+
+    def union(a, b):
+        ra, rb = find(a), find(b)
+        if ra != rb:
+            parent[max(ra, rb)] = min(ra, rb)
+
+    for a in range(n):
+        k = int(h["npass"][a])
+        if k <= 0:
+            continue
+        if d2 is None:
+            union(a, int(h["first"][a]))
+            union(a, int(h["nearest"][a]))
+        else:
+            row = np.asarray(d2[a], dtype=np.float64)
+            thr = np.sort(np.where(np.isnan(row), np.inf, row))[k - 1]
+            for b in np.flatnonzero(row <= thr):
+                union(a, int(b))
+    groups: dict[int, list[int]] = {}
+    for a in range(n):
+        groups.setdefault(find(a), []).append(a)
+    return [g for _, g in sorted(groups.items()) if len(g) >= 2]
 
 
 def chi2_cdf_even(x: float, m: int) -> float:
@@ -572,6 +630,24 @@ class Ensemble:
         _check(self._lib.ekf_gate_lines_device(self._h, ctypes.c_void_p(d_enc or None), ctypes.c_void_p(d_lines or None),
                                                ctypes.c_void_p(d_nlines or None), ctypes.c_void_p(d_hits or None),
                                                ctypes.c_void_p(d_d2 or None)), "ekf_gate_lines_device")
+
+    def gate_landmarks(self, e: int, gate: float, want_d2: bool = False):
+        """Every saved landmark of instance e scored against every other, state untouched (slam_ekf.h
+        ekf_gate_landmarks): the landmark pairs that are one line, in the same direction or flipped
+        (alpha + pi, -r). Returns hits, a [N] array of PAIR_HIT_DTYPE (nearest, first, npass, status,
+        d2_nearest, d2_first, C [3], delta [2]), and with want_d2=True also d2 [N, N] (+inf on the diagonal
+        and at and past savedLineCount). A pair passes when d2 <= gate²; duplicate_clusters groups them."""
+        hits = np.zeros(self.capacity, dtype=PAIR_HIT_DTYPE)
+        d2 = np.zeros((self.capacity, self.capacity)) if want_d2 else None
+        _check(self._lib.ekf_gate_landmarks(self._h, int(e), float(gate), hits.ctypes.data_as(ctypes.c_void_p),
+                                            _dp(d2)), "ekf_gate_landmarks")
+        return (hits, d2) if want_d2 else hits
+
+    def gate_landmarks_device(self, gate: float, d_hits: int, d_d2: int = 0):
+        """gate_landmarks of every instance at once, buffers in device memory (raw pointers: hits [E, N]
+        ekf_pair_hit, d2 [E, N, N] or 0); asynchronous on the context stream."""
+        _check(self._lib.ekf_gate_landmarks_device(self._h, float(gate), ctypes.c_void_p(d_hits or None),
+                                                   ctypes.c_void_p(d_d2 or None)), "ekf_gate_landmarks_device")
 
     def gate_joint(self, e: int, lines, assign, encoder=None, each: bool = False):
         """Joint compatibility of hypotheses against instance e's map, state untouched (slam_ekf.h
